@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- training images/sec of the ACL-GAN step (dis_update + gen_update) at 256x256.
 
-  python bench.py --gpus N --steps K --warmup W [--dtype fp32|bf16|fp16] [--size S --batch B]
+  python bench.py --gpus N --steps K --warmup W [--dtype fp32|bf16|fp16] [--size S --batch B] [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Either the driver launches the ranks (torch.distributed.run; RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or -- when WORLD_SIZE is unset -- this script
@@ -17,6 +17,10 @@ fp32 accumulation, fp32 master weights and Adam, fp16 with dynamic loss scaling.
 
 Timing: K steps bracketed by barrier + synchronize, max over ranks -> `value` / `ms_per_step` (the contract);
 per-step HIP events on the launch stream give `config.ms_per_step_median` (SURVEY.md 8d defines the median).
+Inputs (images, z, initial weights) are seeded, and every warm-up and timed step trains from the state the trainer was built with
+(parameters and Adam state copied back before it): the same arguments give the same inputs and, up to the rounding of the default plan's
+fp32 atomics, the same results on every run.  --dump-outputs DIR keeps what the last timed step computed (see dump_outputs) so that two
+runs or two builds can be compared output for output.
 
 config.other_configs (N = 1, headline workload only): after the timed region, 2 warm-up + 5 timed steps each of the other single-GPU shapes
 BASELINE.json names -- 512x512 fp32 B=4 (configs[3]) and the per-GPU shapes of the two 8-GPU rows, 256x256 bf16 B=8 (configs[2]) and fp16 B=32
@@ -255,6 +259,30 @@ def dominant_kernel_probe(L, dtype, reps=20):
             "frac": round(flop_direct / ms / 1e9 / PEAK[dtype], 4), "traffic": None, "algorithmic_bytes": alg}
 
 
+DUMP_SAMPLE = 1 << 22     # elements kept of the parameters and of the gradients: 2 x 16 MiB of float32, under the 64 MB cap of --dump-outputs
+
+
+def dump_outputs(tr, L, out_dir):
+    """--dump-outputs: what the last timed step computed, as a caller of dis_update / gen_update receives it -- every loss_* attribute
+    (<name>.npy, 0-d), and the parameters after Adam and the gradients of the five networks (params.npy / grads.npy: each tensor in the
+    caller's layout, the networks' tensors in named_parameters() order, concatenated).  float32.  When they hold more than DUMP_SAMPLE
+    elements the same seeded sample of positions is kept from both, so that runs and builds with the same arguments compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name in L.LOSS_NAMES:
+        np.save(os.path.join(out_dir, name + ".npy"), getattr(tr, name).detach().float().cpu().numpy())
+    nets = [getattr(tr, n) for n in tr.NETS]
+    params = torch.cat([v.reshape(-1) for net in nets for _, v in net.named_parameters()])
+    grads = torch.cat([v.reshape(-1) for net in nets for _, v in net.named_grads()])
+    idx = None
+    if params.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(params.numel(), size=DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(params.device)
+    for name, t in (("params", params), ("grads", grads)):
+        np.save(os.path.join(out_dir, name + ".npy"), (t if idx is None else t.index_select(0, idx)).float().cpu().numpy())
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script under torch.distributed.run and relay
     rank 0's output (the one JSON line)."""
@@ -292,8 +320,12 @@ def main():
                     "its lane streams -- what a data-parallel process group (RCCL's stream) or a prefetching loader does to HIP's stream -> hardware-queue placement")
     ap.add_argument("--post-streams", type=int, default=0, help="experiment (round 6): ... or AFTER the trainer exists and before its first update (what a process group "
                     "initialised by the trainer's rank-0 broadcast does)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them computed (losses, a seeded "
+                    "sample of the parameters and gradients) as float32 DIR/<name>.npy, rank 0 only")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.cpu_baseline_worker:
         cpu_baseline_worker()
         return
@@ -390,7 +422,20 @@ def main():
     x_b = (torch.rand(B, 3, S, S, generator=g) * 2 - 1).cuda()
     zs = [[torch.randn(B, 8, 1, 1, generator=g) for _ in range(3)] for _ in range(2)]
 
+    def start_state(t):
+        """the trainer's training state (parameters, Adam moments, 16-bit weight packs, fp16 loss scale) and a copy of it as built"""
+        bufs = [b for grp in (L.GROUP_GEN, L.GROUP_DIS) for b in (t._param[grp], t._m[grp], t._v[grp])]
+        bufs += list(t._w16.values()) + list(t._w16t.values()) + ([t._lscale] if t._lscale is not None else [])
+        return bufs, [b.clone() for b in bufs]
+
+    # Every warm-up and timed step trains from the state the trainer was built with.  The default plan's fp32 atomics sum in a different
+    # order on every run, and chained GAN updates amplify those last bits into different trajectories within a few steps; from one fixed
+    # state, what a step computes is the same on every run up to rounding, so --dump-outputs of two runs or two builds can be compared.
+    state = start_state(tr)
+
     def step():
+        for b, s in zip(*state):
+            b.copy_(s)
         tr.dis_update(x_a, x_b, cfg, z=zs[0])
         tr.gen_update(x_a, x_b, cfg, z=zs[1])
         tr.update_learning_rate()
@@ -416,6 +461,7 @@ def main():
             os.environ["ACLGAN_DDP_OVERLAP"] = "0"
             tr = aclgan_Trainer(cfg, device="cuda:%d" % local_rank, compute_dtype=args.dtype, deterministic=True if args.deterministic else None,
                                 hip_graph=True if args.graph else None)
+            state = start_state(tr)
             step()
             torch.cuda.synchronize()
         log("warm-up step done")
@@ -449,6 +495,8 @@ def main():
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         exposed_ms = float(te.item())
     losses_ok = all(map(lambda n: torch.isfinite(getattr(tr, n)).item(), ["loss_gen_total", "loss_dis_total"]))
+    if args.dump_outputs and rank == 0:      # (before the probes below step `tr` again)
+        dump_outputs(tr, L, args.dump_outputs)
     rccl_info = None
     if use_dist:
         rccl_info = {"overlap_fallback": overlap_fallback, "log": rccl_log,

@@ -152,9 +152,8 @@ int aclgan_get_deterministic(void);
 int aclgan_ctx_create(const aclgan_arch* arch, aclgan_ctx** out);
 void aclgan_ctx_destroy(aclgan_ctx* ctx);
 /* Call once, OUTSIDE any stream capture, on a context whose updates will be captured into a HIP graph (torch.cuda.graph around
- * aclgan_gen_update / aclgan_dis_update): creates the context-private parameter-gradient stream a captured update runs its weight gradients
- * on (a captured update uses one lane; the process-wide lane streams are not captured).  Contexts that never capture should not call it:
- * every additional stream shifts HIP's stream -> hardware-queue placement (measured: 3 ms on the eager fp32 step). */
+ * aclgan_gen_update / aclgan_dis_update).  A captured update runs entirely on the capture stream (one lane, its weight gradients included;
+ * the process-wide lane streams are not captured), so there is nothing to prepare: the call only checks the context. */
 int aclgan_ctx_enable_capture(aclgan_ctx* ctx);
 /* Round 6: create the lane scheduler's process-wide streams (the parameter-gradient stream and lanes 1 .. lanes - 1; lanes <= 0: the current
  * "lanes" setting) on the CURRENT device now rather than at the first update.  HIP binds streams to its hardware queues in creation order;

@@ -15,8 +15,6 @@ PY
 ( timeout 900 python -m pytest tests/test_gpu_lanes.py tests/test_gpu_step16.py tests/test_gpu_ops_misc.py -x -q -s 2>&1 | grep -vE "^\s*$" | tail -60 ) > $OUT/tests.log 2>&1
 for L in 2 3; do timeout 300 $B --lanes $L > $OUT/bench_lanes$L.json 2> $OUT/bench_lanes$L.err; summ $OUT/bench_lanes$L.json; done
 ACLGAN_NORM_MASK=0 timeout 300 $B --lanes 3 --no-launch-floor > $OUT/bench_lanes3_nomask.json 2>/dev/null; summ $OUT/bench_lanes3_nomask.json
-GPU_MAX_HW_QUEUES=8 timeout 300 $B --lanes 3 > $OUT/bench_lanes3_q8.json 2>/dev/null; summ $OUT/bench_lanes3_q8.json
-GPU_MAX_HW_QUEUES=8 timeout 300 $B --lanes 4 > $OUT/bench_lanes4_q8.json 2>/dev/null; summ $OUT/bench_lanes4_q8.json
 # 16-bit: lanes, tile / specialised variants after the round-4 barrier fix
 B16="python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-other-configs --no-launch-floor --config configs/selfie2anime.yaml"
 timeout 300 $B16 --lanes 1 > $OUT/bench_bf16_lanes1.json 2>/dev/null; summ $OUT/bench_bf16_lanes1.json
