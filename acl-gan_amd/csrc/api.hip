@@ -1,5 +1,4 @@
 // api.hip -- error plumbing and the operator-level C ABI of libaclgan_hip (see include/aclgan_hip.h).
-#include <string.h>
 #include "common.h"
 
 #include <cstdarg>
@@ -24,33 +23,6 @@ int hip_fail(hipError_t e, const char* what) {
     return ACLGAN_EHIP;
 }
 
-// scheduler switches (common.h)
-static std::atomic<int> g_lanes{-1}, g_u_batch{-1}, g_norm_mask{-1}, g_mlp_fused{-1};
-static std::atomic<long long> g_tuning_epoch{0};
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return (e && *e) ? atoi(e) : dflt; }
-// (1 .. 3: the updates assign work to lanes 0 .. 2 only; a value of 4 used to be accepted, ran the 3-lane plan and still created a 4th pooled
-//  stream, which shifts HIP's stream -> hardware-queue placement -- clamped since round 6)
-int lanes_setting() { int v = g_lanes.load(); if (v < 0) { v = std::max(1, std::min(3, env_int("ACLGAN_LANES", 3))); g_lanes.store(v); } return v; }
-int set_lanes(int v) { const int old = lanes_setting(); g_lanes.store(std::max(1, std::min(3, v))); return old; }
-int u_batch_setting() { int v = g_u_batch.load(); if (v < 0) { v = env_int("ACLGAN_U_BATCH", 1) ? 1 : 0; g_u_batch.store(v); } return v; }
-int set_u_batch(int v) { const int old = u_batch_setting(); g_u_batch.store(v ? 1 : 0); return old; }
-int norm_mask_setting() { int v = g_norm_mask.load(); if (v < 0) { v = env_int("ACLGAN_NORM_MASK", 1) ? 1 : 0; g_norm_mask.store(v); } return v; }
-int set_norm_mask(int v) { const int old = norm_mask_setting(); g_norm_mask.store(v ? 1 : 0); return old; }
-int mlp_fused_setting() { int v = g_mlp_fused.load(); if (v < 0) { v = env_int("ACLGAN_MLP_FUSED", 1) ? 1 : 0; g_mlp_fused.store(v); } return v; }
-int set_mlp_fused(int v) { const int old = mlp_fused_setting(); g_mlp_fused.store(v ? 1 : 0); return old; }
-static std::atomic<int> g_fault_at{-1};
-int fault_at_setting() { return g_fault_at.load(); }
-int set_fault_at(int v) { return g_fault_at.exchange(v); }
-long long tuning_epoch() { return g_tuning_epoch.load(); }
-void bump_tuning_epoch() { ++g_tuning_epoch; }
-
-static int g_determ = -1;
-bool deterministic() {
-    if (g_determ < 0) { const char* e = getenv("ACLGAN_DETERMINISTIC"); g_determ = (e && atoi(e)) ? 1 : 0; }
-    return g_determ == 1;
-}
-void set_deterministic(int on) { g_determ = on ? 1 : 0; }
-
 }  // namespace aclgan
 
 using namespace aclgan;
@@ -60,8 +32,6 @@ using namespace aclgan;
 namespace aclgan { int gemm_slices_f32(const float* A, const float* Bm, float* Cm, int T, int K, int N, int nslices, int a_mod, hipStream_t st); }
 extern "C" {
 
-int aclgan_set_deterministic(int on) { set_deterministic(on); return ACLGAN_OK; }
-int aclgan_get_deterministic(void) { return deterministic() ? 1 : 0; }
 int aclgan_version(void) { return 300; }   // 0.3.0: 16-bit activation storage, measurement counters
 long long aclgan_launch_count(void) { return g_launches; }
 const char* aclgan_last_error(void) { return g_err; }
@@ -267,50 +237,6 @@ int aclgan_conv2d_fwd16s(const aclgan_conv_desc* d, int dtype, const void* x16, 
     rc = conv_fwd16s(g, dtype, x16, w16, bias, y, y_storage, (hipStream_t)stream);
     if (rc == ACLGAN_EUNSUPPORTED) set_error("conv2d_fwd16s: no 16-bit-storage kernel for this shape (no upsample, Cin and Cout multiples of 64, grid >= 96 tiles)");
     return rc;
-}
-// status in the return value, the previous setting through `previous` (optional): an unknown key is ACLGAN_EINVAL, never a value
-int aclgan_tuning(const char* key, int value, int* previous) {
-    ACL_REQUIRE(key, "aclgan_tuning: null key");
-    int old = 0;
-    if (!strcmp(key, "glds_tile")) old = set_glds_tile(value);
-    else if (!strcmp(key, "wino_x3")) old = set_wino_x3(value);
-    else if (!strcmp(key, "wino_fused")) old = set_wino_fused(value);
-    else if (!strcmp(key, "wino_wgrad_fused")) old = set_wino_wgrad_fused(value);
-    else if (!strcmp(key, "wino_s2k4")) old = set_wino_s2k4(value);
-    else if (!strcmp(key, "dgrad16s_direct")) old = set_dgrad16s_direct(value);
-    else if (!strcmp(key, "fwd16_patch")) old = set_fwd16_patch(value);
-    else if (!strcmp(key, "lanes")) old = set_lanes(value);
-    else if (!strcmp(key, "u_batch")) old = set_u_batch(value);
-    else if (!strcmp(key, "norm_mask")) old = set_norm_mask(value);
-    else if (!strcmp(key, "mlp_fused")) old = set_mlp_fused(value);
-    else if (!strcmp(key, "fault_at")) old = set_fault_at(value);
-    else { set_error("aclgan_tuning: unknown key '%s'", key); return ACLGAN_EINVAL; }
-    bump_tuning_epoch();
-    if (previous) *previous = old;
-    return ACLGAN_OK;
-}
-// read a switch without touching it (no epoch bump, no window in which another thread sees a different value); ACLGAN_EINVAL for an unknown key.
-// key "epoch": the number of aclgan_tuning calls so far (what cached, switch-dependent results are keyed by: workspace sizes)
-int aclgan_tuning_get(const char* key, long long* value) {
-    ACL_REQUIRE(key && value, "aclgan_tuning_get: null argument");
-    if (!strcmp(key, "epoch")) { *value = tuning_epoch(); return ACLGAN_OK; }
-    int old = 0;
-    if (!strcmp(key, "wino_fused")) old = wino_fused_mode();
-    else if (!strcmp(key, "wino_wgrad_fused")) old = wino_wgrad_fused_mode();
-    else if (!strcmp(key, "wino_s2k4")) old = wino_s2k4_setting();
-    else if (!strcmp(key, "lanes")) old = lanes_setting();
-    else if (!strcmp(key, "u_batch")) old = u_batch_setting();
-    else if (!strcmp(key, "norm_mask")) old = norm_mask_setting();
-    else if (!strcmp(key, "mlp_fused")) old = mlp_fused_setting();
-    else if (!strcmp(key, "fault_at")) old = fault_at_setting();
-    else { set_error("aclgan_tuning_get: no getter for key '%s'", key); return ACLGAN_EINVAL; }      // (the 16-bit kernel-variant switches are write-only test knobs)
-    *value = old;
-    return ACLGAN_OK;
-}
-// (round 3 form, kept: the previous value in the return value, -1 for an unknown key)
-int aclgan_set_tuning(const char* key, int value) {
-    int old = 0;
-    return aclgan_tuning(key, value, &old) == ACLGAN_OK ? old : -1;
 }
 int aclgan_conv2d_fwd16s_stats_chunk(const aclgan_conv_desc* d) { ConvGeom g; return (d && make_geom(d, &g) == 0 && conv16_eligible(g, 0)) ? conv_fwd16s_stats_chunk(g) : 0; }
 int aclgan_conv2d_fwd16s_stats(const aclgan_conv_desc* d, int dtype, const void* x16, const void* w16, const float* bias, void* y, int y_storage,

@@ -6,6 +6,7 @@
 #include <string>
 #include <atomic>
 #include "../../include/aclgan_hip.h"
+#include "switches.h"
 
 namespace aclgan {
 
@@ -27,37 +28,15 @@ extern std::atomic<long long> g_launches;
         if (!(cond)) { ::aclgan::set_error(__VA_ARGS__); return ACLGAN_EINVAL; } \
     } while (0)
 
-// Deterministic mode (aclgan_set_deterministic / ACLGAN_DETERMINISTIC=1): every reduction that the default plan combines with fp32
+// Deterministic mode (sw(SW_DETERMINISTIC): aclgan_set_deterministic / ACLGAN_DETERMINISTIC=1): every reduction that the default plan combines with fp32
 // atomics (reflection halo and small-grid split-K of dgrad, the thin / odd-channel weight gradients, bias column sums, LayerNorm
 // parameter gradients, the L1 loss value) takes an ordered path instead -- gradients and losses are reproducible bit for bit run to
 // run, at a few % of step time.  Scratch sizes depend on the mode: set it before sizing workspaces.
-bool deterministic();
-void set_deterministic(int on);
 // out[i] += part[0][i] + part[1][i] + ... (slices added in index order); part is [nslices][n]
 int reduce_slices_ordered(const float* part, int64_t n, int nslices, float* out, hipStream_t st);
 // db[c] += sum over the M rows of dy[M][C], reproducible: row chunks -> part [chunks][C] -> ordered.  part: colsum_ordered_bytes(M, C)
 size_t colsum_ordered_bytes(int64_t M, int C);
 int colsum_ordered(const float* dy, float* db, int64_t M, int C, void* part, hipStream_t st);
-
-// Scheduler switches (aclgan_tuning / environment), read once per update:
-//   lanes (ACLGAN_LANES, default 3): HIP streams the independent branches of an update are spread over (engine.hip); 1 = one queue
-//   u_batch (ACLGAN_U_BATCH, default 1): batched Winograd filter transforms at the start of an update
-int lanes_setting();
-int set_lanes(int v);            // returns the previous value
-int u_batch_setting();
-int set_u_batch(int v);
-//   norm_mask (ACLGAN_NORM_MASK, default 1): the norm backward recomputes ReLU masks from x and the forward's coefficients instead of reading y
-int norm_mask_setting();
-int set_norm_mask(int v);
-//   mlp_fused (ACLGAN_MLP_FUSED, default 1): the generator's MLP forward as one launch (misc.hip: mlp3_fwd) instead of three linear_fwd launches
-int mlp_fused_setting();
-int set_mlp_fused(int v);
-//   fault_at (test hook, default -1 = off): the backward replay fails with ACLGAN_EHIP after its fault_at-th closure has been enqueued --
-//   the error path (lanes and side stream drained before the caller is told) is testable without breaking the GPU
-int fault_at_setting();
-int set_fault_at(int v);
-// every aclgan_tuning call bumps this: cached results that depend on a switch (workspace checks) are keyed by it
-long long tuning_epoch();
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -173,13 +152,7 @@ int conv_wgrad16(const ConvGeom& g, int dtype, const float* x, const float* dy, 
 bool conv16s_ok(const ConvGeom& g, int which);
 // stats (optional, conv_fwd16s_stats_chunk(g) > 0): [B][Ho*Wo / chunk][Co] (mean, M2) pairs of the STORED outputs -- norm_fwd's chunk partials
 int conv_fwd16s_stats_chunk(const ConvGeom& g);
-int set_glds_tile(int v);
-int set_fwd16_patch(int v);
-int set_dgrad16s_direct(int v);
-int set_wino_x3(int v);
 // conv_wino_fused.hip (round 4): Winograd F(4x4,3x3) as ONE launch -- input transform, 36 frequency GEMMs, output transform
-int wino_fused_mode();                           // 0 off, 1 fused where the cost model says it pays, 2 fused wherever eligible
-int set_wino_fused(int v);                       // returns the previous mode
 int wino_fused_force(int on);                    // per-thread: > 0 = eligible shapes take the fused kernel whatever the mode; returns the previous value
 bool wino_fused_ok(int B, int H, int W, int Cin_, int Cout_, int act = ACLGAN_ACT_NONE, int gph = 1, int kph = 1);
 int wino_fused_filter(const float* w, float* Uf, int Co, int Ci, int flip, hipStream_t st, int nph = 1);
@@ -188,8 +161,6 @@ int wino_fused_launch(int B, int H, int W, int Cin_, int Cout_, const float* in,
 int wino_fused_up5_fwd(int B, int Hi, int Wi, int Cin_, int Cout_, const float* x, const float* Uf, const float* bias, float* y, int Hf, int Wf, int act,
                        hipStream_t st);
 // conv_wino_wgrad_fused.hip (round 4): the Winograd weight / bias gradient of the 3x3 ResBlock layers as one kernel + one finish launch
-int wino_wgrad_fused_mode();                     // 0 off, 1 where the cost model says it pays, 2 wherever eligible
-int set_wino_wgrad_fused(int v);                 // returns the previous mode
 bool wino_wgrad_fused_ok(const ConvGeom& g);
 size_t wino_wgrad_fused_scratch_bytes(const ConvGeom& g);
 int wino_wgrad_fused(const ConvGeom& g, const float* x, const float* dy, float* dw, float* db, void* scratch, hipStream_t st);
@@ -202,8 +173,6 @@ int wino_fused_s2k4_fwd(int B, int Hi, int Wi, int Ci, int Co, const float* x, c
 int wino_fused_s2k4_dgrad(int B, int Hi, int Wi, int Ci, int Co, const float* dy, const float* Uf, float* dx, int accumulate, hipStream_t st);
 // ... and their conv-level wrappers (conv_wino.hip): which = 0 forward, 1 input gradient (interior of the padded grid; never in deterministic mode)
 bool conv_s2k4_wino_ok(const ConvGeom& g, int which);
-int wino_s2k4_setting();                        // tuning switch "wino_s2k4": 1 = on (default), 0 = the stride-2 layers keep the direct kernels
-int set_wino_s2k4(int v);
 size_t conv_s2k4_wino_scratch_bytes(const ConvGeom& g);
 int conv_fwd_s2k4_wino(const ConvGeom& g, const float* x, const float* w, const float* bias, float* y, void* scratch, hipStream_t st, float* stats = nullptr);
 int conv_dgrad_s2k4_wino_interior(const ConvGeom& g, const float* dy, const float* w, float* dx, int accumulate, void* scratch, hipStream_t st);

@@ -800,7 +800,7 @@ static size_t wgrad_generic_det_bytes(const ConvGeom& g) {
 
 size_t conv_wgrad_scratch_bytes(const ConvGeom& g) {
     const size_t b = std::max(conv_wgrad_fast_scratch_bytes(g), conv_wgrad_small_scratch_bytes(g));
-    return (deterministic() && !conv_wgrad_fast_supported(g)) ? std::max(b, wgrad_generic_det_bytes(g)) : b;    // general kernel: slice copies
+    return (sw(SW_DETERMINISTIC) && !conv_wgrad_fast_supported(g)) ? std::max(b, wgrad_generic_det_bytes(g)) : b;    // general kernel: slice copies
 }
 
 int conv_wgrad(const ConvGeom& g, const float* x, const float* dy, float* dw, float* db, hipStream_t st, void* scratch, const float* haveV) {
@@ -820,7 +820,7 @@ int conv_wgrad(const ConvGeom& g, const float* x, const float* dy, float* dw, fl
         if (rc == ACLGAN_OK) db = nullptr;   // bias gradient fused into the tuned kernel
         if (rc == ACLGAN_EUNSUPPORTED) {
             void* det = nullptr;
-            if (deterministic()) {
+            if (sw(SW_DETERMINISTIC)) {
                 if (!scratch) { set_error("conv_wgrad: deterministic mode needs the scratch buffer (aclgan_conv2d_wgrad_ws)"); return ACLGAN_EINVAL; }
                 det = scratch;
             }
@@ -830,7 +830,7 @@ int conv_wgrad(const ConvGeom& g, const float* x, const float* dy, float* dw, fl
         }
         if (rc) return rc;
     }
-    if (db && deterministic()) {      // ordered column sums (the kernels below add their row blocks with fp32 atomics)
+    if (db && sw(SW_DETERMINISTIC)) {      // ordered column sums (the kernels below add their row blocks with fp32 atomics)
         if (!scratch) { set_error("conv_wgrad: deterministic mode needs the scratch buffer (aclgan_conv2d_wgrad_ws)"); return ACLGAN_EINVAL; }
         int splits, chunk;
         wgrad_generic_plan(1, g.M, &splits, &chunk);

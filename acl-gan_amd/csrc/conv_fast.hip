@@ -240,7 +240,7 @@ int launch_fwd_fast(const ConvGeom& g, FwdFP p, hipStream_t st) {
     p.part = nullptr;
     const int nk = g.K / BK;
     if (p.ring > 0 && (p.act != ACLGAN_ACT_NONE || g.Co % 4 != 0)) splits = 1, p.nkz = nk;   // ring + activation: single pass
-    if (deterministic()) splits = 1, p.nkz = nk;                                             // no partial buffer: the slices would meet in atomics
+    if (sw(SW_DETERMINISTIC)) splits = 1, p.nkz = nk;                                             // no partial buffer: the slices would meet in atomics
     if (splits > 1 && p.ring > 0) {
         hipLaunchKernelGGL(ring_zero_kernel, dim3(cdiv(rows * (g.Co / 4), 256)), dim3(256), 0, st, p, rows);
         ACL_CHECK_LAUNCH("ring_zero_kernel");
@@ -439,7 +439,6 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_dgrad_fast_kernel(DgFP pk) 
     }
 }
 
-int halo_split_override();
 template <int WM, int WN, int TM, int TN>
 int launch_dgrad_fast(const ConvGeom& g, DgFP p, hipStream_t st) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -464,9 +463,9 @@ int launch_dgrad_fast(const ConvGeom& g, DgFP p, hipStream_t st) {
     // halo launches loop over the useful taps only (about 1 / taps-per-axis of them): plan the slices for that shorter loop --
     // every slice ends in 128 x 128 fp32 atomics, which is what the old 15-slice halo launch mostly consisted of
     const int nk_plan = (p.mode == 2 && p.band == 0) ? std::max(g.Co / 16, nk_min / ((g.k + g.s - 1) / g.s)) : nk_min;
-    if (nblk < 128 && nk_plan >= 32 && !deterministic() && !p.ringpad)       // (the slices combine with fp32 atomics; ringpad: one plain store per position)
+    if (nblk < 128 && nk_plan >= 32 && !sw(SW_DETERMINISTIC) && !p.ringpad)       // (the slices combine with fp32 atomics; ringpad: one plain store per position)
         p.ksplit = max(1, min(nk_plan / 8, 512 / nblk));   // floor: stay within one round of 512 resident workgroups
-    if (p.mode == 2 && p.band == 0 && !p.ringpad && !deterministic() && halo_split_override() > 0) p.ksplit = std::min(halo_split_override(), nk_plan);
+    if (p.mode == 2 && p.band == 0 && !p.ringpad && !sw(SW_DETERMINISTIC) && sw(SW_HALO_SPLIT) > 0) p.ksplit = std::min(sw(SW_HALO_SPLIT), nk_plan);
     if (p.ksplit > 1 && p.mode == 0) {
         hipError_t e = hipMemsetAsync(p.dxp, 0, conv_dgrad_scratch_bytes(g), st);
         if (e != hipSuccess) return hip_fail(e, "memset dxp");
@@ -489,9 +488,7 @@ int launch_dgrad_fast_merged(const ConvGeom& g, DgFP p, hipStream_t st) {
     // OPT-IN (ACLGAN_MERGEDHALO=1).  Measured (profiles/r02_experiments.md): correct, but slower -- the 34 halo tiles are a second,
     // nearly empty round after the 512 interior workgroups (one full tile duration of tail), and the divergent atomic/plain
     // epilogue of the interior tiles costs more than the 36-48 us launch it removes: fp32 step 171.7 -> 182.5 ms.
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("ACLGAN_MERGEDHALO"); off = (e && atoi(e)) ? 0 : 1; }
-    if (off || deterministic() || g.p == 0 || g.Ci % 4 != 0) return ACLGAN_EUNSUPPORTED;
+    if (!sw(SW_MERGEDHALO) || sw(SW_DETERMINISTIC) || g.p == 0 || g.Ci % 4 != 0) return ACLGAN_EUNSUPPORTED;
     int mi = 0, mh = 0;
     for (int cy = 0; cy < g.s; ++cy)
         for (int cx = 0; cx < g.s; ++cx) {
@@ -523,21 +520,11 @@ int launch_dgrad_fast_merged(const ConvGeom& g, DgFP p, hipStream_t st) {
 // slices; 64 x 64: 54.7 (1) / 39.3 (2) / 35.0 (3); 64 x 128: **34.3** (planned: 6) / 36.4 (3); 128 x 64: 35.9 (6) / 38.7 (3).  No shape gets under
 // ~34 us: the ring is a fixed cost of prologue (tap lists), a short dependent loop and the mirrored atomics.  Default: 64 x 128 on the 3x3
 // stride-1 layers (what was measured), the caller's tile elsewhere.  ACLGAN_HALO_TILE = 1 / 2 / 3 forces 64 x 64 / 64 x 128 / 128 x 64 on every
-// layer with Cin % 64 == 0, 4 = the caller's tile everywhere; ACLGAN_HALO_SPLIT overrides the slice count.
-static int halo_tile_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_HALO_TILE"); v = e ? atoi(e) : 0; if (v < 0 || v > 4) v = 0; }
-    return v;
-}
-int halo_split_override() {
-    static int v = -2;
-    if (v == -2) { const char* e = getenv("ACLGAN_HALO_SPLIT"); v = e ? atoi(e) : 0; }
-    return v;
-}
+// layer with Cin % 64 == 0, 4 = the caller's tile everywhere; ACLGAN_HALO_SPLIT overrides the slice count (launch_dgrad_fast).
 template <int WM, int WN, int TM, int TN>
 int launch_dgrad_halo(const ConvGeom& g, DgFP p, hipStream_t st) {
     if (p.band == 0 && !p.ringpad && g.Ci % 64 == 0) {
-        int t = halo_tile_mode();
+        int t = sw(SW_HALO_TILE);
         if (t == 0 && g.k == 3 && g.s == 1 && g.Ci % 128 == 0 && WM == 2 && WN == 2 && TM == 2 && TN == 2) t = 2;
         if (t == 1) return launch_dgrad_fast<2, 2, 1, 1>(g, p, st);       // 64 x 64
         if (t == 2) return launch_dgrad_fast<2, 2, 1, 2>(g, p, st);       // 64 x 128
@@ -550,7 +537,7 @@ template <int WM, int WN, int TM, int TN>
 int dgrad_fast_all(const ConvGeom& g, DgFP p, float* dxp, float* dx, int accumulate, bool* direct, hipStream_t st) {
     // deterministic mode: the Winograd layers keep their fast interior and fold the ring in order (below); every other layer
     // takes the padded-grid plan -- one launch, one writer per element, then the fold gather
-    if (g.up == 0 && dx != nullptr && (!deterministic() || g.p == 0 || (dxp && conv_wino_ok(g)))) {
+    if (g.up == 0 && dx != nullptr && (!sw(SW_DETERMINISTIC) || g.p == 0 || (dxp && conv_wino_ok(g)))) {
         // interior positions straight into dx (balanced grid, no scratch round trip) and the halo ring mirrored in with
         // atomics: together = dgrad + reflection_pad2d backward
         *direct = true;
@@ -562,7 +549,7 @@ int dgrad_fast_all(const ConvGeom& g, DgFP p, float* dxp, float* dx, int accumul
              : (dxp && conv_s2k4_wino_ok(g, 1)) ? conv_dgrad_s2k4_wino_interior(g, p.dy, p.w, dx, accumulate, dxp, st)      // 4x4 stride 2: four parity phases
                                       : launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
         if (rc) return rc;
-        if (g.p > 0 && deterministic()) {
+        if (g.p > 0 && sw(SW_DETERMINISTIC)) {
             // ordered reflection backward: the ring positions are STORED on a zeroed padded grid (one writer each; the scratch is
             // free again -- the Winograd planes of the interior are consumed) and conv_fold adds them onto their targets
             hipError_t e = hipMemsetAsync(dxp, 0, (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float), st);
@@ -883,18 +870,8 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_wgrad_kc_kernel(WgFP pk, Wg
     }
 }
 
-// ACLGAN_BIGTILE=1: 256 x 128 workgroup tiles with 8 waves for forward / dgrad of the large layers (25 % fewer operand bytes per
-// MFMA than 128 x 128; one workgroup per CU)
-bool big_tiles() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_BIGTILE"); v = (e && atoi(e)) ? 1 : 0; }
-    return v == 1;
-}
-
 bool wgrad_kc_ok(const ConvGeom& g) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("ACLGAN_NOWGKC"); off = (e && atoi(e)) ? 1 : 0; }
-    return !off && g.Co % 64 == 0 && g.Ci % 64 == 0;
+    return !sw(SW_NOWGKC) && g.Co % 64 == 0 && g.Ci % 64 == 0;
 }
 
 template <int WM, int WN, int TM, int TN>
@@ -951,9 +928,7 @@ int launch_wgrad_fast(const ConvGeom& g, WgFP p, hipStream_t st, void* det_part 
         p.dw = (float*)det_part; p.dw_zs = ndw;
         if (p.db) { p.db = (float*)det_part + (size_t)splits * ndw; p.db_zs = g.Co; }
     }
-    static int nost = -1;
-    if (nost < 0) { const char* e = getenv("ACLGAN_NOSINGLETAP"); nost = (e && atoi(e)) ? 1 : 0; }
-    if (!nost && p.Ci % BN == 0) hipLaunchKernelGGL((conv_wgrad_fast_kernel<WM, WN, TM, TN, true>), dim3(p.nwg, ny, splits), dim3(WM * WN * 64), 0, st, p);
+    if (!sw(SW_NOSINGLETAP) && p.Ci % BN == 0) hipLaunchKernelGGL((conv_wgrad_fast_kernel<WM, WN, TM, TN, true>), dim3(p.nwg, ny, splits), dim3(WM * WN * 64), 0, st, p);
     else hipLaunchKernelGGL((conv_wgrad_fast_kernel<WM, WN, TM, TN, false>), dim3(p.nwg, ny, splits), dim3(WM * WN * 64), 0, st, p);
     ACL_CHECK_LAUNCH("conv_wgrad_fast_kernel");
     if (p.dw_zs) {
@@ -1049,11 +1024,6 @@ int up5_wgrad_t(const ConvGeom& g, const float* x, const float* dy, float* dw, f
 // alias into the band, instead of fp32 atomics.  MEASURED SLOWER (round 6, profiles/r06_experiments.md): the step 82.9 against 82.3 ms (3 lanes),
 // 90.5 against 90.1 (one queue) -- the ring launch is bound by its k loop and its tail, not by the atomics; the extra launch and the 25 MB
 // round trip cost more than the atomics did.  Off; kept as a measured option (the deterministic mode uses the full-grid fold as before).
-bool up5_band_fold() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_UP5_BANDFOLD"); v = (e && atoi(e)) ? 1 : 0; }
-    return v == 1;
-}
 template <int WM, int WN, int TM, int TN>
 int up5_dgrad_t(const ConvGeom& g, const float* dy, const float* w, float* dx, int accumulate, float* wp, hipStream_t st) {
     const int64_t nm = (int64_t)4 * g.Co * 9 * (g.Ci / 4);
@@ -1088,7 +1058,7 @@ int up5_dgrad_t(const ConvGeom& g, const float* dy, const float* w, float* dx, i
     p.Ho = g.Ho; p.Wo = g.Wo; p.k = 5; p.s = 1; p.Hp = g.Hp; p.Wp = g.Wp; p.Hc = g.Hp; p.Wc = g.Wp;
     p.mode = 2; p.accumulate = 1; p.pad = 2; p.Hi = g.Hu; p.Wi = g.Wu;
     p.dyv = 0; p.band = 6; p.upshift = 1; p.Hd = g.Hi; p.Wd = g.Wi;
-    if (deterministic()) {     // band positions stored on a zeroed padded hi-res grid (after the merged filters), then the fold gather
+    if (sw(SW_DETERMINISTIC)) {     // band positions stored on a zeroed padded hi-res grid (after the merged filters), then the fold gather
         float* dxp = (float*)((char*)wp + up5_merged_bytes(g));
         hipError_t e = hipMemsetAsync(dxp, 0, (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float), st);
         if (e != hipSuccess) return hip_fail(e, "memset padded grid");
@@ -1097,7 +1067,7 @@ int up5_dgrad_t(const ConvGeom& g, const float* dy, const float* w, float* dx, i
         if (rc) return rc;
         return conv_fold(g, dxp, dx, 1, st);
     }
-    if (up5_band_fold() && g.Ci % 4 == 0) {
+    if (sw(SW_UP5_BANDFOLD) && g.Ci % 4 == 0) {
         // Round 6: one plain store per band position into the (otherwise untouched) padded hi-res scratch, then a gather over the dx pixels
         // that alias into the band -- instead of 6.2 M fp32 atomics per launch (256 -> 128 layer at 256x256 B=8: 445 us for 13 GFLOP)
         float* dxp = (float*)((char*)wp + up5_merged_bytes(g));
@@ -1117,29 +1087,29 @@ size_t conv_up5_scratch_bytes(const ConvGeom& g) {
 }
 // dgrad of a sub-pixel layer: merged phase filters, then the Winograd planes of its four phases
 size_t conv_up5_dgrad_scratch_bytes(const ConvGeom& g) {
-    if (!fast_enabled() || !up5_eligible(g)) return 0;
-    const size_t padded = (deterministic() || up5_band_fold()) ? (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float) : 0;     // ring positions on the padded hi-res grid (ordered fold / band fold)
+    if (sw(SW_NOFAST) || !up5_eligible(g)) return 0;
+    const size_t padded = (sw(SW_DETERMINISTIC) || sw(SW_UP5_BANDFOLD)) ? (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float) : 0;     // ring positions on the padded hi-res grid (ordered fold / band fold)
     return up5_merged_bytes(g) + std::max(conv_up5_wino_dgrad_scratch_bytes(g), padded);
 }
 // weight-gradient scratch of the tuned kernels: phase gradients of the sub-pixel layers + the partial tiles of the
 // ordered-slice kernel (0 when neither applies)
 size_t conv_wgrad_fast_scratch_bytes(const ConvGeom& g) {
-    if (!fast_enabled()) return 0;
+    if (sw(SW_NOFAST)) return 0;
     if (wgrad_kc_ok(g) && conv_wino_ok(g)) return conv_wgrad_wino_scratch_bytes(g);
     if (wgrad_kc_ok(g)) return ((wgrad_part_scratch(g, BK, WGKC_TARGET) + 255) & ~(size_t)255) + (up5_eligible(g) ? conv_up5_wino_wgrad_scratch_bytes(g) : 0);
-    if (deterministic()) return wgrad_fast_det_bytes(g, g.K, g.M, 1);      // atomics kernel with per-slice copies (the sub-pixel split is skipped)
+    if (sw(SW_DETERMINISTIC)) return wgrad_fast_det_bytes(g, g.K, g.M, 1);      // atomics kernel with per-slice copies (the sub-pixel split is skipped)
     return conv_up5_scratch_bytes(g);
 }
 // forward scratch: merged phase weights + ring split-K partials (sub-pixel layers), or the split-K partials of a small-grid layer
 size_t conv_fwd_fast_scratch_bytes(const ConvGeom& g) {
-    if (!fast_enabled()) return 0;
+    if (sw(SW_NOFAST)) return 0;
     if (conv_wino_ok(g)) return conv_wino_scratch_bytes(g);
     if (up5_eligible(g)) return up5_merged_bytes(g) + ((fwd_partial_bytes(g, 2, BK) + 255) & ~(size_t)255) + conv_up5_wino_fwd_scratch_bytes(g);
     return std::max(fwd_partial_bytes(g, 0, BK), conv_s2k4_wino_scratch_bytes(g));
 }
 
 int conv_up5_fwd(const ConvGeom& g, const float* x, const float* w, const float* bias, float* y, void* scratch, hipStream_t st, float* keepV) {
-    if (!fast_enabled() || !up5_eligible(g) || !scratch) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_NOFAST) || !up5_eligible(g) || !scratch) return ACLGAN_EUNSUPPORTED;
     if (g.Co > 64) return up5_fwd_t<2, 2, 2, 2>(g, x, w, bias, y, (float*)scratch, st, keepV);
     if (g.Co > 32) return up5_fwd_t<4, 1, 2, 2>(g, x, w, bias, y, (float*)scratch, st, keepV);
     return up5_fwd_t<4, 1, 2, 1>(g, x, w, bias, y, (float*)scratch, st, keepV);
@@ -1147,18 +1117,16 @@ int conv_up5_fwd(const ConvGeom& g, const float* x, const float* w, const float*
 
 // needs conv_up5_scratch_bytes(g) of scratch; dx complete on return (no fold kernel)
 int conv_up5_dgrad(const ConvGeom& g, const float* dy, const float* w, float* dx, int accumulate, void* scratch, hipStream_t st) {
-    if (!fast_enabled() || !up5_eligible(g) || !scratch) return ACLGAN_EUNSUPPORTED;
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("ACLGAN_NOUP5DGRAD"); off = (e && atoi(e)) ? 1 : 0; }
-    if (off) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_NOFAST) || !up5_eligible(g) || !scratch) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_NOUP5DGRAD)) return ACLGAN_EUNSUPPORTED;
     if (g.Ci > 64) return up5_dgrad_t<2, 2, 2, 2>(g, dy, w, dx, accumulate, (float*)scratch, st);
     if (g.Ci > 32) return up5_dgrad_t<4, 1, 2, 2>(g, dy, w, dx, accumulate, (float*)scratch, st);
     return up5_dgrad_t<4, 1, 2, 1>(g, dy, w, dx, accumulate, (float*)scratch, st);
 }
 
 int conv_up5_wgrad(const ConvGeom& g, const float* x, const float* dy, float* dw, float* db, void* scratch, hipStream_t st, const float* haveV) {
-    if (!fast_enabled() || !up5_eligible(g) || !scratch || !dw) return ACLGAN_EUNSUPPORTED;
-    if (deterministic() && !wgrad_kc_ok(g)) return ACLGAN_EUNSUPPORTED;    // (the phase / ring launches of the atomics kernel share dw)
+    if (sw(SW_NOFAST) || !up5_eligible(g) || !scratch || !dw) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_DETERMINISTIC) && !wgrad_kc_ok(g)) return ACLGAN_EUNSUPPORTED;    // (the phase / ring launches of the atomics kernel share dw)
     if (g.Co > 64) return up5_wgrad_t<2, 2, 2, 2>(g, x, dy, dw, db, (float*)scratch, st, haveV);
     if (g.Co > 32) return up5_wgrad_t<2, 2, 1, 2>(g, x, dy, dw, db, (float*)scratch, st, haveV);
     return up5_wgrad_t<1, 4, 1, 2>(g, x, dy, dw, db, (float*)scratch, st, haveV);
@@ -1180,8 +1148,7 @@ int gemm_slices_f32(const float* A, const float* Bm, float* Cm, int T, int K, in
         // K is short here (the channel count): 128 x 128 tiles leave 1.5 rounds of workgroups and exposed prologues/epilogues;
         // 64 x 128 tiles at 4 workgroups per CU measured 8 % faster on the ResBlock shape (profiles/r02_experiments.md).
         // ACLGAN_GEMM_VAR=1: 128 x 64 tiles, 3 per CU;  =2: 128 x 128 tiles, 3 per CU.
-        static int var = -1;
-        if (var < 0) { const char* e = getenv("ACLGAN_GEMM_VAR"); var = e ? atoi(e) : 0; }
+        const int var = sw(SW_GEMM_VAR);
         if (var == 1) {
             p.tiles_n = cdiv(N, 64); p.nwg = cdiv(T, 128) * p.tiles_n;
             hipLaunchKernelGGL((conv_fwd_fast_kernel<2, 2, 2, 1, 3>), dim3(p.nwg, nslices, 1), dim3(256), 0, st, p);
@@ -1209,23 +1176,19 @@ int gemm_slices_f32(const float* A, const float* Bm, float* Cm, int T, int K, in
 // the Winograd output transform holds whole 4x4 output tiles per thread: it can emit the (mean, M2) partials of the following
 // normalisation layer at no extra pass over y.  ACLGAN_NOSTATFUSE=1 keeps the separate statistics kernel.
 int conv_fwd_stats_chunk(const ConvGeom& g) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("ACLGAN_NOSTATFUSE"); off = (e && atoi(e)) ? 1 : 0; }
-    if (off || !fast_enabled() || g.Ci % 16 != 0 || g.act != ACLGAN_ACT_NONE) return 0;
+    if (sw(SW_NOSTATFUSE) || sw(SW_NOFAST) || g.Ci % 16 != 0 || g.act != ACLGAN_ACT_NONE) return 0;
     if (conv_wino_ok(g)) return 16;
     return (g.Ho % 4 == 0 && g.Wo % 4 == 0 && conv_s2k4_wino_ok(g, 0)) ? 16 : 0;      // (round 6: the 4x4 stride-2 layers through the fused kernel)
 }
 // bytes of the Winograd input transform conv_fwd can leave behind for conv_wgrad (same path selection as conv_fwd / conv_wgrad)
 size_t conv_fwd_keep_bytes(const ConvGeom& g) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("ACLGAN_NOKEEPV"); off = (e && atoi(e)) ? 1 : 0; }
-    if (off || !fast_enabled() || !wgrad_kc_ok(g)) return 0;
+    if (sw(SW_NOKEEPV) || sw(SW_NOFAST) || !wgrad_kc_ok(g)) return 0;
     if (up5_eligible(g)) return conv_up5_wino_wgrad_scratch_bytes(g) ? conv_up5_wino_keep_bytes(g) : 0;
     if (g.Ci % 16 != 0 || !conv_wino_ok(g) || !conv_wgrad_wino_scratch_bytes(g)) return 0;
     return conv_wino_keep_bytes(g);
 }
 int conv_fwd_fast(const ConvGeom& g, const float* x, const float* w, const float* bias, float* y, hipStream_t st, void* scratch, float* stats, float* keepV) {
-    if (!fast_enabled() || g.Ci % 16 != 0) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_NOFAST) || g.Ci % 16 != 0) return ACLGAN_EUNSUPPORTED;
     if (scratch && conv_wino_ok(g)) return conv_fwd_wino(g, x, w, bias, y, scratch, st, stats, keepV);   // 3x3 ResBlock convs: Winograd F(4x4,3x3)
     if (scratch && !keepV && conv_s2k4_wino_ok(g, 0) && (!stats || (g.Ho % 4 == 0 && g.Wo % 4 == 0)))      // 4x4 stride-2 layers: four parity phases of the same kernel
         return conv_fwd_s2k4_wino(g, x, w, bias, y, scratch, st, stats);
@@ -1237,7 +1200,8 @@ int conv_fwd_fast(const ConvGeom& g, const float* x, const float* w, const float
     p.Hi = g.Hi; p.Wi = g.Wi; p.Ci = g.Ci; p.Ho = g.Ho; p.Wo = g.Wo; p.Co = g.Co; p.k = g.k; p.s = g.s; p.p = g.p;
     p.up = g.up; p.Hu = g.Hu; p.Wu = g.Wu; p.M = g.M; p.K = g.K; p.act = g.act; p.tiles_n = 0; p.nwg = 0; p.nkz = 0;
     p.B = g.B; p.ring = 0; p.phases = 0; p.Hf = 0; p.Wf = 0;
-    if (g.Co % 128 == 0 && big_tiles() && g.M >= 256 * 128) return launch_fwd_fast<4, 2, 2, 2>(g, p, st);   // 256 x 128, 8 waves (experiment)
+    // ACLGAN_BIGTILE=1: 256 x 128 tiles with 8 waves for the large layers (25 % fewer operand bytes per MFMA than 128 x 128; one workgroup per CU)
+    if (g.Co % 128 == 0 && sw(SW_BIGTILE) && g.M >= 256 * 128) return launch_fwd_fast<4, 2, 2, 2>(g, p, st);   // 256 x 128, 8 waves (experiment)
     if (g.Co > 64) return launch_fwd_fast<2, 2, 2, 2>(g, p, st);
     if (g.Co > 32) return launch_fwd_fast<4, 1, 2, 2>(g, p, st);
     return launch_fwd_fast<4, 1, 2, 1>(g, p, st);
@@ -1247,18 +1211,16 @@ int conv_fwd_fast(const ConvGeom& g, const float* x, const float* w, const float
 // been fully produced here (no fold kernel needed).
 int conv_dgrad_fast(const ConvGeom& g, const float* dy, const float* w, float* dxp, float* dx, int accumulate, bool* direct, hipStream_t st) {
     *direct = false;
-    if (!fast_enabled() || g.Co % 16 != 0 || g.Ci % 4 != 0) return ACLGAN_EUNSUPPORTED;
-    static int nodirect = -1;
-    if (nodirect < 0) { const char* e = getenv("ACLGAN_NODIRECT"); nodirect = (e && atoi(e)) ? 1 : 0; }
-    if (nodirect) dx = nullptr;
-    if (deterministic() && !dxp) { set_error("conv_dgrad: deterministic mode needs the scratch buffer"); return ACLGAN_EINVAL; }
+    if (sw(SW_NOFAST) || g.Co % 16 != 0 || g.Ci % 4 != 0) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_NODIRECT)) dx = nullptr;
+    if (sw(SW_DETERMINISTIC) && !dxp) { set_error("conv_dgrad: deterministic mode needs the scratch buffer"); return ACLGAN_EINVAL; }
     DgFP p;
     p.dy = dy; p.w = w; p.dxp = dxp;
     p.Ho = g.Ho; p.Wo = g.Wo; p.Co = g.Co; p.Ci = g.Ci; p.k = g.k; p.s = g.s; p.Hp = g.Hp; p.Wp = g.Wp;
     p.Hc = cdiv(g.Hp, g.s); p.Wc = cdiv(g.Wp, g.s); p.Mc = 0; p.tiles_n = 0; p.nwg = 0; p.ksplit = 1;
     p.mode = 0; p.accumulate = 0; p.pad = g.p; p.B = g.B; p.Hi = g.Hu; p.Wi = g.Wu;
     p.dyv = 0; p.py = 0; p.px = 0; p.Hf = 0; p.Wf = 0; p.band = 0; p.upshift = 0; p.Hd = g.Hu; p.Wd = g.Wu;
-    if (g.Ci % 128 == 0 && big_tiles() && g.M >= 256 * 128) return dgrad_fast_all<4, 2, 2, 2>(g, p, dxp, dx, accumulate, direct, st);
+    if (g.Ci % 128 == 0 && sw(SW_BIGTILE) && g.M >= 256 * 128) return dgrad_fast_all<4, 2, 2, 2>(g, p, dxp, dx, accumulate, direct, st);
     if (g.Ci > 64) return dgrad_fast_all<2, 2, 2, 2>(g, p, dxp, dx, accumulate, direct, st);
     if (g.Ci > 32) return dgrad_fast_all<4, 1, 2, 2>(g, p, dxp, dx, accumulate, direct, st);
     return dgrad_fast_all<4, 1, 2, 1>(g, p, dxp, dx, accumulate, direct, st);
@@ -1284,9 +1246,9 @@ int gemm_at_b_slices_f32(const float* A, const float* Bm, float* Cm, int T, int 
     return launch_wgrad_kc_any(g, p, part, st);
 }
 
-bool conv_wgrad_fast_supported(const ConvGeom& g) { return fast_enabled() && g.Co % 4 == 0 && g.Ci % 4 == 0; }
+bool conv_wgrad_fast_supported(const ConvGeom& g) { return !sw(SW_NOFAST) && g.Co % 4 == 0 && g.Ci % 4 == 0; }
 int conv_wgrad_fast(const ConvGeom& g, const float* x, const float* dy, float* dw, float* db, hipStream_t st, void* scratch, const float* haveV) {
-    if (!fast_enabled() || g.Co % 4 != 0 || g.Ci % 4 != 0) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_NOFAST) || g.Co % 4 != 0 || g.Ci % 4 != 0) return ACLGAN_EUNSUPPORTED;
     WgFP p;
     p.fsl = 0; p.fsx_mod = 0; p.fs_x = p.fs_dy = 0;
     p.x = x; p.dy = dy; p.dw = dw; p.db = db;
@@ -1298,7 +1260,7 @@ int conv_wgrad_fast(const ConvGeom& g, const float* x, const float* dy, float* d
     // the scratch-less operator call keeps the atomics kernel
     if (wgrad_kc_ok(g) && (scratch || wgrad_part_scratch(g, BK, WGKC_TARGET) == 0)) return launch_wgrad_kc_any(g, p, scratch, st);
     void* det = nullptr;
-    if (deterministic()) {
+    if (sw(SW_DETERMINISTIC)) {
         if (!scratch) { set_error("conv_wgrad: deterministic mode needs the scratch buffer (aclgan_conv2d_wgrad_ws)"); return ACLGAN_EINVAL; }
         det = scratch;
     }
@@ -1327,7 +1289,7 @@ double pipe_flops(int B, int OH, int OW, int Cin_, int Cout_, int slices) { retu
 double conv_exec_flops(const ConvGeom& g, int which, bool f16) {
     const double direct = 2.0 * (double)g.M * g.Co * g.K;
     const double ringpix = (double)g.Ho * g.Wo - (double)std::max(0, g.Ho - 4) * std::max(0, g.Wo - 4);      // output ring of width 2 (sub-pixel layers)
-    if (up5_eligible(g) && fast_enabled()) {
+    if (up5_eligible(g) && !sw(SW_NOFAST)) {
         const double ring_fwd = 2.0 * g.B * ringpix * g.Co * g.K;
         // input gradient: band of width 6 of the padded hi-res grid, ~9 of the 25 taps useful per position (tap lists, conv_fast_common.h::dg_row)
         const double band = (double)g.Hp * g.Wp - (double)std::max(0, g.Hp - 12) * std::max(0, g.Wp - 12);
@@ -1342,7 +1304,7 @@ double conv_exec_flops(const ConvGeom& g, int which, bool f16) {
         const double phases = 4.0 * 2.0 * g.B * (g.Hi - 2.0) * (g.Wi - 2.0) * g.Co * 9.0 * g.Ci;
         return phases + (which == 1 ? ring_dg : ring_fwd);
     }
-    if (!f16 && fast_enabled() && g.Ci % 16 == 0 && conv_wino_ok(g)) {
+    if (!f16 && !sw(SW_NOFAST) && g.Ci % 16 == 0 && conv_wino_ok(g)) {
         const double halo = 2.0 * g.B * ((double)g.Hp * g.Wp - (double)g.Hi * g.Wi) * g.Ci * g.Co * 3.0;      // ring of the padded grid, 3 of 9 taps per position
         if (which == 0) return wino_fused_ok(g.B, g.Hi, g.Wi, g.Ci, g.Co, g.act) && !conv_fwd_keep_bytes(g) ? fused_flops(g.B, g.Hi, g.Wi, g.Ci, g.Co, 1, 1)
                                                                                                               : pipe_flops(g.B, g.Hi, g.Wi, g.Ci, g.Co, 1);
@@ -1350,7 +1312,7 @@ double conv_exec_flops(const ConvGeom& g, int which, bool f16) {
         if (wgrad_kc_ok(g) && conv_wgrad_wino_scratch_bytes(g)) return pipe_flops(g.B, g.Hi, g.Wi, g.Ci, g.Co, 1);
         return direct;
     }
-    if (!f16 && fast_enabled() && which < 2 && conv_s2k4_wino_ok(g, which)) {
+    if (!f16 && !sw(SW_NOFAST) && which < 2 && conv_s2k4_wino_ok(g, which)) {
         if (which == 0) return fused_flops(g.B, g.Ho, g.Wo, g.Ci, g.Co, 1, 4);
         const double halo = 2.0 * g.B * ((double)g.Hp * g.Wp - (double)g.Hi * g.Wi) * g.Ci * g.Co * 2.0;      // 2 of the 4 taps of a parity class per ring position
         return fused_flops(g.B, g.Ho, g.Wo, g.Co, g.Ci, 4, 1) + halo;

@@ -457,7 +457,7 @@ int launch_dgrad16(const ConvGeom& g, DgFP p, hipStream_t st) {
     const int nblk = p.nwg * g.s * g.s;
     p.ksplit = 1;
     const int nk_plan = (p.mode == 2 && p.band == 0) ? std::max(g.Co / (16 * KS), nk_min / ((g.k + g.s - 1) / g.s)) : nk_min;   // halo: useful taps only
-    if (nblk < 128 && nk_plan * KS >= 32 && !deterministic()) p.ksplit = max(1, min(nk_plan * KS / 8, 512 / nblk));   // (slices combine with atomics)
+    if (nblk < 128 && nk_plan * KS >= 32 && !sw(SW_DETERMINISTIC)) p.ksplit = max(1, min(nk_plan * KS / 8, 512 / nblk));   // (slices combine with atomics)
     if (p.ksplit > 1 && p.mode == 1 && !p.accumulate) {
         hipError_t e = hipMemsetAsync(p.dxp, 0, (size_t)g.B * g.Hi * g.Wi * g.Ci * sizeof(float), st);
         if (e != hipSuccess) return hip_fail(e, "memset dx");
@@ -474,9 +474,7 @@ int launch_dgrad16_merged(const ConvGeom& g, DgFP p, hipStream_t st) {
     // OPT-IN (ACLGAN_MERGEDHALO=1).  Measured (profiles/r02_experiments.md): correct, but slower -- the 34 halo tiles are a second,
     // nearly empty round after the 512 interior workgroups (one full tile duration of tail), and the divergent atomic/plain
     // epilogue of the interior tiles costs more than the 36-48 us launch it removes: fp32 step 171.7 -> 182.5 ms.
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("ACLGAN_MERGEDHALO"); off = (e && atoi(e)) ? 0 : 1; }
-    if (off || deterministic() || g.p == 0) return ACLGAN_EUNSUPPORTED;
+    if (!sw(SW_MERGEDHALO) || sw(SW_DETERMINISTIC) || g.p == 0) return ACLGAN_EUNSUPPORTED;
     int mi = 0, mh = 0;
     for (int cy = 0; cy < g.s; ++cy)
         for (int cx = 0; cx < g.s; ++cx) {
@@ -775,17 +773,10 @@ __global__ void up5_merge16_kernel(const float* __restrict__ w, u16* __restrict_
     }
 }
 
-// ACLGAN_TILE16=wide: 128 x 256 tiles (8 waves) for the 256-channel layers (A/B switch; default off, see launch_fwd16_ks)
-bool wide_tiles() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_TILE16"); v = (e && e[0] == 'w') ? 1 : 0; }
-    return v == 1;
-}
-
 // ---- eligibility ----
-bool fwd16_ok(const ConvGeom& g) { return fast_enabled() && g.Ci % 32 == 0 && g.Co % 32 == 0 && (g.up == 0 || up5_eligible(g)); }
-bool dgrad16_ok(const ConvGeom& g) { return fast_enabled() && g.Ci % 32 == 0 && g.Co % 32 == 0 && (g.up == 0 || up5_eligible(g)); }
-bool wgrad16_ok(const ConvGeom& g) { return fast_enabled() && g.Co % 64 == 0 && g.Ci % 64 == 0 && (g.up == 0 || up5_eligible(g)); }
+bool fwd16_ok(const ConvGeom& g) { return !sw(SW_NOFAST) && g.Ci % 32 == 0 && g.Co % 32 == 0 && (g.up == 0 || up5_eligible(g)); }
+bool dgrad16_ok(const ConvGeom& g) { return !sw(SW_NOFAST) && g.Ci % 32 == 0 && g.Co % 32 == 0 && (g.up == 0 || up5_eligible(g)); }
+bool wgrad16_ok(const ConvGeom& g) { return !sw(SW_NOFAST) && g.Co % 64 == 0 && g.Ci % 64 == 0 && (g.up == 0 || up5_eligible(g)); }
 
 size_t up5_w16_bytes(const ConvGeom& g) { return ((size_t)4 * g.Co * 9 * g.Ci * sizeof(u16) + 255) & ~(size_t)255; }
 
@@ -808,7 +799,7 @@ template <class T, int KS>
 int launch_fwd16_ks(const ConvGeom& g, const FwdFP& p, hipStream_t st) {
     // (a 128 x 256 tile with 8 waves -- every activation row fetched once per tap -- was measured: the isolated ResBlock
     //  kernel gains 9 %, the whole step loses 2 %: ACLGAN_TILE16=wide keeps it selectable)
-    if (g.Co % 256 == 0 && wide_tiles()) return launch_fwd16<T, KS, 2, 4, 2, 2>(g, p, st);
+    if (g.Co % 256 == 0 && sw(SW_TILE16)) return launch_fwd16<T, KS, 2, 4, 2, 2>(g, p, st);
     if (g.Co > 64) return launch_fwd16<T, KS, 2, 2, 2, 2>(g, p, st);
     return launch_fwd16<T, KS, 4, 1, 2, 2>(g, p, st);      // Co 32 / 64: 256 x 64
 }
@@ -818,13 +809,13 @@ int launch_fwd16_any(const ConvGeom& g, const FwdFP& p, hipStream_t st) {
 }
 template <class T, int KS>
 int launch_dgrad16_ks(const ConvGeom& g, const DgFP& p, hipStream_t st) {
-    if (g.Ci % 256 == 0 && wide_tiles()) return launch_dgrad16<T, KS, 2, 4, 2, 2>(g, p, st);
+    if (g.Ci % 256 == 0 && sw(SW_TILE16)) return launch_dgrad16<T, KS, 2, 4, 2, 2>(g, p, st);
     if (g.Ci > 64) return launch_dgrad16<T, KS, 2, 2, 2, 2>(g, p, st);
     return launch_dgrad16<T, KS, 4, 1, 2, 2>(g, p, st);
 }
 template <class T, int KS>
 int launch_dgrad16_merged_ks(const ConvGeom& g, const DgFP& p, hipStream_t st) {
-    if (g.Ci % 256 == 0 && wide_tiles()) return launch_dgrad16_merged<T, KS, 2, 4, 2, 2>(g, p, st);
+    if (g.Ci % 256 == 0 && sw(SW_TILE16)) return launch_dgrad16_merged<T, KS, 2, 4, 2, 2>(g, p, st);
     if (g.Ci > 64) return launch_dgrad16_merged<T, KS, 2, 2, 2, 2>(g, p, st);
     return launch_dgrad16_merged<T, KS, 4, 1, 2, 2>(g, p, st);
 }
@@ -882,7 +873,7 @@ DgFP dg_params(const ConvGeom& g, const float* dy, const u16* w16t, float* dx) {
 
 template <class T>
 int dgrad16_t(const ConvGeom& g, const float* dy, const float* w, const u16* w16t, float* dx, int accumulate, void* scratch, hipStream_t st) {
-    if (deterministic()) {
+    if (sw(SW_DETERMINISTIC)) {
         // every padded-grid position has exactly one writer (no split-K, no mirrored halo); conv_fold gathers the reflection /
         // upsample backward.  The sub-pixel layers run as the plain upsample + 5x5 convolution they are: at 16-bit MFMA rates
         // one launch over the padded grid beats interior + zeroed ring + accumulate-fold (measured: bf16 step 76.8 vs 81.2 ms).
@@ -983,7 +974,7 @@ size_t conv_fwd16_scratch_bytes(const ConvGeom& g) {
 }
 size_t conv_dgrad16_scratch_bytes(const ConvGeom& g) {
     if (!dgrad16_ok(g)) return 0;
-    if (deterministic()) return (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float);     // padded-grid gradient
+    if (sw(SW_DETERMINISTIC)) return (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float);     // padded-grid gradient
     return up5_eligible(g) ? up5_w16_bytes(g) : 0;
 }
 size_t conv_wgrad16_scratch_bytes(const ConvGeom& g) { return wgrad16_ok(g) ? std::max(wgrad16_scratch(g), conv_wgrad16s_scratch_bytes(g)) : 0; }

@@ -123,8 +123,7 @@ static void fwd_split_plan(int rows, int Co, int K, int bk, int* splits, int* nk
     const int BM = Co > 64 ? 128 : 256, BN = Co > 64 ? 128 : (Co > 32 ? 64 : 32);
     const int nwg = cdiv(rows, BM) * cdiv(Co, BN), nk = K / bk;
     int sp = 1;
-    static int thr = -1;      // grids below this many workgroups split K (ACLGAN_SPLIT_NWG; default 256 = one workgroup per CU; 128 through round 3: round 4 measured 98.4 -> 97.5 ms per fp32 step)
-    if (thr < 0) { const char* e = getenv("ACLGAN_SPLIT_NWG"); thr = e ? atoi(e) : 256; }
+    const int thr = sw(SW_SPLIT_NWG);      // grids below this many workgroups split K (default 256 = one workgroup per CU; 128 through round 3: round 4 measured 98.4 -> 97.5 ms per fp32 step)
     if (nwg < thr && nk * bk >= 512) sp = max(1, min(nk * bk / 128, 512 / nwg));   // floor: 512 = one full round at 2 workgroups per CU
     *nkz = cdiv(nk, sp);
     *splits = cdiv(nk, *nkz);
@@ -349,19 +348,8 @@ __global__ void up5_scatter_kernel(const float* __restrict__ dwp, float* __restr
     }
 }
 
-bool up5_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_NOUP5"); v = (e && atoi(e)) ? 0 : 1; }
-    return v == 1;
-}
 bool up5_eligible(const ConvGeom& g) {
-    return up5_enabled() && g.up == 1 && g.k == 5 && g.p == 2 && g.s == 1 && g.Ci % 16 == 0 && g.Co % 16 == 0 && g.Hi >= 4 && g.Wi >= 4;
-}
-
-bool fast_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_NOFAST"); v = (e && atoi(e)) ? 0 : 1; }
-    return v == 1;
+    return !sw(SW_NOUP5) && g.up == 1 && g.k == 5 && g.p == 2 && g.s == 1 && g.Ci % 16 == 0 && g.Co % 16 == 0 && g.Hi >= 4 && g.Wi >= 4;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -651,13 +651,7 @@ __global__ void __launch_bounds__(512, 1) conv_fwd16p_kernel(FwdSP p) {
     }
 #endif
 }
-// shapes the patch kernel takes, and whether it is on (aclgan_tuning "fwd16_patch" / ACLGAN_FWD16_PATCH; default: see launch_fwd16s)
-std::atomic<int> g_fwd16_patch{-1};
-int fwd16_patch_mode() {
-    int v = g_fwd16_patch.load();
-    if (v < 0) { const char* e = getenv("ACLGAN_FWD16_PATCH"); v = e ? atoi(e) : 1; if (v < 0 || (v & 15) > 2) v = 1; g_fwd16_patch.store(v); }
-    return v;
-}
+// shapes the patch kernel takes (whether it is on: aclgan_tuning "fwd16_patch" / ACLGAN_FWD16_PATCH; default: see launch_fwd16s)
 bool fwd16p_shape_ok(const ConvGeom& g) {
     if (!(g.k == 3 && g.s == 1 && g.p == 1 && g.up == 0 && g.Hi == g.Ho && g.Wi == g.Wo)) return false;
     if (!(g.Wo == 32 || g.Wo == 64) || (g.Ho * g.Wo) % 256 != 0 || g.Ho < 2) return false;
@@ -671,10 +665,8 @@ bool fwd16p_shape_ok(const ConvGeom& g) {
 // 186.7 -- one 8-wave workgroup per CU has nothing to run while it waits at its barrier, two 4-wave workgroups cover each other.  So:
 // 128-row tiles by default; ACLGAN_GLDS_TILE = 2 / 3 forces 256 x 128 / 256 x 256 where the shape allows, 4 = the largest-tile rule
 // (kept tested: tests/test_gpu_ops16s.py runs every tile).  Returns 1 / 2 / 3.
-std::atomic<int> g_tile_force{-1};      // (atomics: a switch set while another thread plans an update is seen old or new, never torn)
 int glds_tile(int rows, int N) {
-    int force = g_tile_force.load();
-    if (force < 0) { const char* e = getenv("ACLGAN_GLDS_TILE"); force = e ? atoi(e) : 0; if (force < 0) force = 0; g_tile_force.store(force); }
+    const int force = sw(SW_GLDS_TILE);
     const int t256 = N % 256 == 0 ? cdiv(rows, 256) * (N / 256) : 0, t128 = N % 128 == 0 ? cdiv(rows, 256) * (N / 128) : 0;
     if (force == 3 && t256) return 3;
     if (force == 2 && t128) return 2;
@@ -689,18 +681,13 @@ int glds_tile(int rows, int N) {
 // ACLGAN_GLDS_SPEC = 1: the wave-specialised kernels instead of the unified ones (every wave copies and multiplies).  Measured: the
 // specialised 128 x 128 kernel is SLOWER (ResBlock forward 69 vs 54 us; bf16 step 65.5 vs 57.2 ms), the 256 x 128 one wins isolated
 // (50.3 vs 52.7 us) and loses in the step (60.1 vs 57.2 ms) -- profiles/r03_experiments.md; kept as a tested option
-int g_spec = -1;
-bool glds_spec() {
-    if (g_spec < 0) { const char* e = getenv("ACLGAN_GLDS_SPEC"); g_spec = e ? atoi(e) : 0; }
-    return g_spec != 0;
-}
 
 template <class T>
 int launch_fwd16s(const ConvGeom& g, FwdSP p, hipStream_t st) {
-    if (fwd16_patch_mode() && fwd16p_shape_ok(g)) {      // 3x3 ResBlock shapes: the input patch stays in LDS for all nine taps
+    if (sw(SW_FWD16_PATCH) && fwd16p_shape_ok(g)) {      // 3x3 ResBlock shapes: the input patch stays in LDS for all nine taps
         p.tiles_n = g.Co / 128; p.nwg = (g.M / 256) * p.tiles_n;
 #ifdef ACLGAN_FWD16P_ABLATION
-        const int abl = fwd16_patch_mode() >> 4;
+        const int abl = sw(SW_FWD16_PATCH) >> 4;
         if (abl == 1) { hipLaunchKernelGGL((conv_fwd16p_kernel<T, 2, 2, 1, 1>), dim3(p.nwg), dim3(512), 0, st, p); ACL_CHECK_LAUNCH("abl"); return ACLGAN_OK; }
         if (abl == 2) { hipLaunchKernelGGL((conv_fwd16p_kernel<T, 2, 2, 1, 2>), dim3(p.nwg), dim3(512), 0, st, p); ACL_CHECK_LAUNCH("abl"); return ACLGAN_OK; }
         if (abl == 4) { hipLaunchKernelGGL((conv_fwd16p_kernel<T, 2, 2, 1, 4>), dim3(p.nwg), dim3(512), 0, st, p); ACL_CHECK_LAUNCH("abl"); return ACLGAN_OK; }
@@ -709,15 +696,14 @@ int launch_fwd16s(const ConvGeom& g, FwdSP p, hipStream_t st) {
         if (abl == 5) { hipLaunchKernelGGL((conv_fwd16p_kernel<T, 2, 2, 1, 5>), dim3(p.nwg), dim3(512), 0, st, p); ACL_CHECK_LAUNCH("abl"); return ACLGAN_OK; }
         if (abl == 3) { hipLaunchKernelGGL((conv_fwd16p_kernel<T, 2, 2, 1, 3>), dim3(p.nwg), dim3(512), 0, st, p); ACL_CHECK_LAUNCH("abl"); return ACLGAN_OK; }
 #endif
-        if ((fwd16_patch_mode() & 15) == 2) hipLaunchKernelGGL((conv_fwd16p_kernel<T, 2, 2, 1>), dim3(p.nwg), dim3(512), 0, st, p);      // counter-phase form (measured alternative)
+        if ((sw(SW_FWD16_PATCH) & 15) == 2) hipLaunchKernelGGL((conv_fwd16p_kernel<T, 2, 2, 1>), dim3(p.nwg), dim3(512), 0, st, p);      // counter-phase form (measured alternative)
         else hipLaunchKernelGGL((conv_fwd16p_kernel<T, 2, 2, 0>), dim3(p.nwg), dim3(512), 0, st, p);
         ACL_CHECK_LAUNCH("conv_fwd16p_kernel");
         return ACLGAN_OK;
     }
     const int tc = glds_tile(g.M, g.Co);
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("ACLGAN_GLDS_NBUF"); force = e ? atoi(e) : 0; }
-    const bool sp = glds_spec();
+    const int nbuf = sw(SW_GLDS_NBUF);
+    const bool sp = sw(SW_GLDS_SPEC) != 0;
     if (tc == 3) {
         p.tiles_n = g.Co / 256; p.nwg = cdiv(g.M, 256) * p.tiles_n;
         hipLaunchKernelGGL((conv_fwd16s_kernel<T, 4, 2, 4, 2, 0>), dim3(p.nwg), dim3(512), 0, st, p);
@@ -730,7 +716,7 @@ int launch_fwd16s(const ConvGeom& g, FwdSP p, hipStream_t st) {
         p.tiles_n = g.Co / BN; p.nwg = cdiv(g.M, 128) * p.tiles_n;
         // (the single-buffer variant, 4 workgroups per CU, wins on ISOLATED large grids -- B=32 ResBlock shape 173 vs 200 us -- but loses
         //  badly inside the step: fp16 B=32 step 237.6 vs 185.0 ms, profiles/r03_experiments.md; ACLGAN_GLDS_NBUF=1 selects it)
-        if (BN == 128 && force == 1) hipLaunchKernelGGL((conv_fwd16s_kernel<T, 2, 2, 2, 1, 0>), dim3(p.nwg), dim3(256), 0, st, p);
+        if (BN == 128 && nbuf == 1) hipLaunchKernelGGL((conv_fwd16s_kernel<T, 2, 2, 2, 1, 0>), dim3(p.nwg), dim3(256), 0, st, p);
         else if (BN == 128 && sp) hipLaunchKernelGGL((conv_fwd16s_kernel<T, 2, 2, 2, 2, 2>), dim3(p.nwg), dim3(384), 0, st, p);      // 4 consumers + 2 producers, 2 x 32 KB, 2 workgroups per CU
         else if (BN == 128) hipLaunchKernelGGL((conv_fwd16s_kernel<T, 2, 2, 2, 2, 0>), dim3(p.nwg), dim3(256), 0, st, p);
         else if (sp) hipLaunchKernelGGL((conv_fwd16s_kernel<T, 2, 2, 1, 2, 2>), dim3(p.nwg), dim3(384), 0, st, p);
@@ -893,7 +879,7 @@ template <class T>
 int launch_dgrad16s(const ConvGeom& g, DgSP p, hipStream_t st) {
     const int tc = glds_tile(p.Mc * g.s * g.s, g.Ci);      // (rows of all stride-parity classes together fill the chip)
     const dim3 z(1, 1, g.s * g.s);
-    const bool sp = glds_spec();
+    const bool sp = sw(SW_GLDS_SPEC) != 0;
     if (tc == 3) {
         p.tiles_n = g.Ci / 256; p.nwg = cdiv(p.Mc, 256) * p.tiles_n;
         hipLaunchKernelGGL((conv_dgrad16s_kernel<T, 4, 2, 4, 2, 0>), dim3(p.nwg, 1, z.z), dim3(512), 0, st, p);
@@ -944,7 +930,6 @@ __global__ void __launch_bounds__(256) conv_fold_st_kernel(FoldSP f) {
 }
 
 bool shape_ok(const ConvGeom& g);
-bool enabled();
 
 // ------------------------------------------------------------------------------------------
 // wgrad on 16-bit x and dy:  dW[co][tap][ci] = sum over pixels of dy[p][co] * x[src(p, tap)][ci]
@@ -1147,23 +1132,16 @@ WgSPlan wgrad16s_plan(const ConvGeom& g) {
     return q;
 }
 bool wgrad16s_shape_ok(const ConvGeom& g) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("ACLGAN_NOWGRAD16S"); off = (e && atoi(e)) ? 1 : 0; }
+    const int off = sw(SW_NOWGRAD16S);
     // (with the parallel bias finish it wins at every size measured against the register-transposing kernel: B=8 ResBlock 69.5 vs 117.7 us,
     //  CE2 62.6 vs 101.7, discriminator 128->256 / 256->512 51.5 / 48.3 vs 77.9 / 76.7, 16x16 maps 26.3 vs 34.9, B=32 214 vs 408 us;
     //  ACLGAN_WGRAD16S_MINPIX sets a pixel-count threshold)
-    static int minpix = -1;
-    if (minpix < 0) { const char* e = getenv("ACLGAN_WGRAD16S_MINPIX"); minpix = e ? atoi(e) : 64; }
-    return !off && enabled() && shape_ok(g) && g.Co % 128 == 0 && g.Ci % 128 == 0 && g.M >= std::max(64, minpix);
+    const int minpix = sw(SW_WGRAD16S_MINPIX);
+    return !off && !sw(SW_NOGLDS16) && shape_ok(g) && g.Co % 128 == 0 && g.Ci % 128 == 0 && g.M >= std::max(64, minpix);
 }
 
 bool shape_ok(const ConvGeom& g) {
-    return fast_enabled() && g.up == 0 && g.Ci % 64 == 0 && g.Co % 64 == 0 && g.k >= 1 && g.p < g.Hi && g.p < g.Wi;
-}
-bool enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_NOGLDS16"); v = (e && atoi(e)) ? 0 : 1; }
-    return v == 1;
+    return !sw(SW_NOFAST) && g.up == 0 && g.Ci % 64 == 0 && g.Co % 64 == 0 && g.k >= 1 && g.p < g.Hi && g.p < g.Wi;
 }
 
 }  // namespace
@@ -1173,22 +1151,9 @@ bool enabled() {
 // ------------------------------------------------------------------------------------------
 // which: 0 forward, 1 dgrad.  The forward also wants a grid that fills the chip without split-K (small late-discriminator maps keep the
 // split-K kernel of conv_fast16.hip, which reads the same 16-bit activations through its A16 path).
-// tuning / test knob behind aclgan_set_tuning("dgrad16s_direct", v); returns the previous value
-static std::atomic<int> g_dgrad_direct{-1};
-int set_dgrad16s_direct(int v) {
-    if (g_dgrad_direct.load() < 0) { const char* e = getenv("ACLGAN_DGRAD16S_DIRECT"); g_dgrad_direct.store(e ? (atoi(e) ? 1 : 0) : 0); }
-    return g_dgrad_direct.exchange(v ? 1 : 0);
-}
-// tuning knob "fwd16_patch": 1 = the 3x3 stride-1 layers it fits run on conv_fwd16p_kernel (input patch resident in LDS), 0 = on conv_fwd16s
-int set_fwd16_patch(int v) { const int old = fwd16_patch_mode(); g_fwd16_patch.store((v < 0 || (v & 15) > 2) ? 1 : v); return old; }
-// tuning / test knob behind aclgan_set_tuning("glds_tile", v): same values as ACLGAN_GLDS_TILE; returns the previous value
-int set_glds_tile(int v) {
-    if (g_tile_force.load() < 0) glds_tile(1, 1);
-    return g_tile_force.exchange(v < 0 ? 0 : v);
-}
 
 bool conv16s_ok(const ConvGeom& g, int which) {
-    if (!enabled() || !shape_ok(g)) return false;
+    if (sw(SW_NOGLDS16) || !shape_ok(g)) return false;
     if (which == 0) {
         const int BN = g.Co % 128 == 0 ? 128 : 64;
         return cdiv(g.M, 128) * (g.Co / BN) >= 96 || g.K <= 1024;      // (a grid that fills the chip without split-K)
@@ -1198,10 +1163,8 @@ bool conv16s_ok(const ConvGeom& g, int which) {
 
 // > 0: conv_fwd16s can emit the normalisation statistics of its output ((mean, M2) per 128-pixel chunk and channel) from its epilogue
 int conv_fwd16s_stats_chunk(const ConvGeom& g) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("ACLGAN_NOSTATFUSE"); off = (e && atoi(e)) ? 1 : 0; }
-    if (off || !conv16s_ok(g, 0)) return 0;
-    const int rows = (fwd16_patch_mode() && fwd16p_shape_ok(g)) ? 256 : (glds_tile(g.M, g.Co) >= 2 ? 256 : 128);      // the statistics chunk is the launch's row tile
+    if (sw(SW_NOSTATFUSE) || !conv16s_ok(g, 0)) return 0;
+    const int rows = (sw(SW_FWD16_PATCH) && fwd16p_shape_ok(g)) ? 256 : (glds_tile(g.M, g.Co) >= 2 ? 256 : 128);      // the statistics chunk is the launch's row tile
     return (g.Ho * g.Wo) % rows == 0 ? rows : 0;
 }
 
@@ -1236,8 +1199,7 @@ int conv_dgrad16s(const ConvGeom& g, int dtype, const void* dy16, const void* w1
     // direct mode (ACLGAN_DGRAD16S_DIRECT=1): pixels without mirrored partners skip the scratch round trip, the fold touches the border band
     // only.  Bit-identical results (197 operator / step / determinism tests pass with it on) and no measurable gain: bf16 step 55.2 vs 55.2 ms,
     // fp16 B=32 184.1 vs 185.6 (same box, back to back) -- the fold was not on the critical path.  Off by default.
-    int direct_on = g_dgrad_direct.load();
-    if (direct_on < 0) { const char* e = getenv("ACLGAN_DGRAD16S_DIRECT"); direct_on = e ? (atoi(e) ? 1 : 0) : 0; g_dgrad_direct.store(direct_on); }
+    const int direct_on = sw(SW_DGRAD16S_DIRECT);
     p.dx = dx; p.Hi = g.Hi; p.Wi = g.Wi; p.pad = g.p; p.accumulate = accumulate;
     p.direct = (direct_on && dxst == dtype && g.Ci % 2 == 0) ? 1 : 0;
     int rc;

@@ -529,12 +529,6 @@ __global__ void __launch_bounds__(256) colsum4_kernel(const f32x4* __restrict__ 
     }
 }
 
-bool small_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_NOSMALL"); v = (e && atoi(e)) ? 0 : 1; }
-    return v == 1;
-}
-
 }  // namespace
 
 // ---------------- round 6: input gradient of the first discriminator layers (4x4 stride 2 pad 1, Cin 3 / 6 <- Cout 64; networks.py:41) ----------------
@@ -700,12 +694,6 @@ __global__ void __launch_bounds__(256, 2) conv_thin_in2_kernel(const float* __re
     }
 }
 
-static bool thin_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_NOTHIN"); v = (e && atoi(e)) ? 0 : 1; }
-    return v == 1;
-}
-
 // tiles per workgroup of conv_thin_in2_kernel: the most that still leaves two workgroups per CU
 static int thin_in2_tpw(int B, int tx, int ty) {
     for (int t = 4; t > 1; t >>= 1)
@@ -719,27 +707,21 @@ static int launch_thin_in2(const ConvGeom& g, const float* x, const float* w, co
     ACL_CHECK_LAUNCH("conv_thin_in2_kernel");
     return ACLGAN_OK;
 }
-// ACLGAN_THININ2=0: the round-2 kernel for the 7x7 layers, the general kernels for the first discriminator layers (A/B switch)
-static bool thin_in2_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_THININ2"); v = (e && !atoi(e)) ? 0 : 1; }
-    return v == 1;
-}
 int conv_fwd_small(const ConvGeom& g, const float* x, const float* w, const float* bias, float* y, hipStream_t st) {
     // round 6: the first discriminator layers (4x4 stride 2 reflect pad 1, Cin 3 / 6 -> 64: networks.py:41)
-    if (small_enabled() && thin_enabled() && thin_in2_enabled() && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && g.Co == 64 && (g.Ci == 3 || g.Ci == 6) &&
+    if (!sw(SW_NOSMALL) && !sw(SW_NOTHIN) && sw(SW_THININ2) && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && g.Co == 64 && (g.Ci == 3 || g.Ci == 6) &&
         g.Hi >= 2 && g.Wi >= 2)
         return g.Ci == 3 ? launch_thin_in2<3, 4, 2, 1>(g, x, w, bias, y, st) : launch_thin_in2<6, 4, 2, 1>(g, x, w, bias, y, st);
-    if (!small_enabled() || g.s != 1 || g.up || g.k != 7 || g.p != 3 || g.Hu < g.k || g.Wu < g.k) return ACLGAN_EUNSUPPORTED;
-    if (thin_enabled() && g.Co <= 4 && g.Ci % 8 == 0) {
+    if (sw(SW_NOSMALL) || g.s != 1 || g.up || g.k != 7 || g.p != 3 || g.Hu < g.k || g.Wu < g.k) return ACLGAN_EUNSUPPORTED;
+    if (!sw(SW_NOTHIN) && g.Co <= 4 && g.Ci % 8 == 0) {
         const int tx = cdiv(g.Wi, TW), ty = cdiv(g.Hi, TH);
         hipLaunchKernelGGL(conv_thin_out_kernel<0>, dim3(g.B * tx * ty), dim3(256), 0, st, x, w, bias, y, g.Hi, g.Wi, g.Ci, g.Co, g.act, tx, ty);
         ACL_CHECK_LAUNCH("conv_thin_out_kernel<fwd>");
         return ACLGAN_OK;
     }
-    if (thin_enabled() && thin_in2_enabled() && g.Co == 64 && (g.Ci == 3 || g.Ci == 4))
+    if (!sw(SW_NOTHIN) && sw(SW_THININ2) && g.Co == 64 && (g.Ci == 3 || g.Ci == 4))
         return g.Ci == 3 ? launch_thin_in2<3, 7, 1, 3>(g, x, w, bias, y, st) : launch_thin_in2<4, 7, 1, 3>(g, x, w, bias, y, st);
-    if (thin_enabled() && g.Co == 64 && (g.Ci == 3 || g.Ci == 4)) {
+    if (!sw(SW_NOTHIN) && g.Co == 64 && (g.Ci == 3 || g.Ci == 4)) {
         const int tx = cdiv(g.Wi, TW), ty = cdiv(g.Hi, TH);
         const dim3 grid(g.B * tx * ((ty + 1) / 2));
         if (g.Ci == 3) hipLaunchKernelGGL((conv_thin_in_kernel<3>), grid, dim3(256), 0, st, x, w, bias, y, g.Hi, g.Wi, g.act, tx, ty);
@@ -757,7 +739,7 @@ int conv_fwd_small(const ConvGeom& g, const float* x, const float* w, const floa
 // dgrad of a thin-input 7x7 layer onto the padded grid dxp [B][H+6][W+6][Ci] (the caller folds the reflection)
 int conv_dgrad_small(const ConvGeom& g, const float* dy, const float* w, float* dxp, hipStream_t st) {
     // round 6: ... and of the first discriminator layers (4x4 stride 2 pad 1) onto [B][H+2][W+2][Ci]
-    if (small_enabled() && thin_enabled() && thin_in2_enabled() && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && (g.Ci == 3 || g.Ci == 6) && g.Co % 4 == 0 &&
+    if (!sw(SW_NOSMALL) && !sw(SW_NOTHIN) && sw(SW_THININ2) && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && (g.Ci == 3 || g.Ci == 6) && g.Co % 4 == 0 &&
         g.Hi % 2 == 0 && g.Wi % 2 == 0) {
         const int64_t nthr = (int64_t)g.B * ((g.Hp + 1) / 2) * ((g.Wp + 1) / 2);
         const dim3 grid((unsigned)cdiv64(nthr, 256));
@@ -766,7 +748,7 @@ int conv_dgrad_small(const ConvGeom& g, const float* dy, const float* w, float* 
         ACL_CHECK_LAUNCH("conv_s2k4_thin_dgrad_kernel");
         return ACLGAN_OK;
     }
-    if (!small_enabled() || !thin_enabled() || g.s != 1 || g.up || g.k != 7 || g.p != 3) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_NOSMALL) || sw(SW_NOTHIN) || g.s != 1 || g.up || g.k != 7 || g.p != 3) return ACLGAN_EUNSUPPORTED;
     if (g.Ci > 4 || g.Co % 8 != 0) return ACLGAN_EUNSUPPORTED;
     const int tx = cdiv(g.Wi + 6, TW), ty = cdiv(g.Hi + 6, TH);
     hipLaunchKernelGGL(conv_thin_out_kernel<1>, dim3(g.B * tx * ty), dim3(256), 0, st, dy, w, (const float*)nullptr, dxp, g.Hi, g.Wi, g.Co, g.Ci,
@@ -776,7 +758,7 @@ int conv_dgrad_small(const ConvGeom& g, const float* dy, const float* w, float* 
 }
 
 static bool thin_wgrad_case(const ConvGeom& g, bool* wide_x) {
-    if (!small_enabled() || !thin_enabled() || g.s != 1 || g.up || g.k != 7 || g.p != 3 || g.Hi < 7 || g.Wi < 7) return false;
+    if (sw(SW_NOSMALL) || sw(SW_NOTHIN) || g.s != 1 || g.up || g.k != 7 || g.p != 3 || g.Hi < 7 || g.Wi < 7) return false;
     if (g.Co == 64 && g.Ci <= 4) { *wide_x = false; return true; }
     if (g.Co == 4 && g.Ci == 64) { *wide_x = true; return true; }
     return false;
@@ -789,16 +771,16 @@ size_t conv_wgrad_small_scratch_bytes(const ConvGeom& g) {
     if (!thin_wgrad_case(g, &wx)) return 0;
     const dim3 gr = thin_wgrad_grid(g, wx);
     const size_t nwg = (size_t)gr.x * gr.y * gr.z;
-    if (deterministic())       // + second-level partials + the ordered bias column sums
+    if (sw(SW_DETERMINISTIC))       // + second-level partials + the ordered bias column sums
         return (nwg + cdiv((int)nwg, 64)) * 49 * 256 * sizeof(float) + 256 + colsum_ordered_bytes(g.M, g.Co);
     return nwg * 49 * 256 * sizeof(float);
 }
 
 int conv_wgrad_small(const ConvGeom& g, const float* x, const float* dy, float* dw, float* db, hipStream_t st, void* scratch) {
-    if (!small_enabled() || g.s != 1 || g.up || g.k != 7 || g.p != 3 || g.Hi < 7 || g.Wi < 7) return ACLGAN_EUNSUPPORTED;
+    if (sw(SW_NOSMALL) || g.s != 1 || g.up || g.k != 7 || g.p != 3 || g.Hi < 7 || g.Wi < 7) return ACLGAN_EUNSUPPORTED;
     bool wx = false;
     const bool thin = thin_wgrad_case(g, &wx);
-    const bool det = deterministic();
+    const bool det = sw(SW_DETERMINISTIC);
     if (det && !scratch) { set_error("conv_wgrad: deterministic mode needs the scratch buffer (aclgan_conv2d_wgrad_ws)"); return ACLGAN_EINVAL; }
     if (thin && (dw != nullptr || !wx)) {
         ACL_REQUIRE(dw != nullptr, "conv_wgrad(thin): dw must be given");

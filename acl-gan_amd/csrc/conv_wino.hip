@@ -442,50 +442,23 @@ __global__ void __launch_bounds__(256) wino_filtergrad_kernel(const float* __res
     }
 }
 
-bool wino_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_NOWINO"); v = (e && atoi(e)) ? 0 : 1; }
-    return v == 1;
-}
-bool wino_up5_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_NOWINOUP5"); v = (e && atoi(e)) ? 0 : 1; }
-    return v == 1;
-}
-
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 int grid_for(int64_t n, int cap) { return (int)std::min<int64_t>(cdiv64(n, 256), cap); }
 const int WINO_BIAS_BLOCKS = 1024;       // x 256 threads: a multiple of every channel-group count in {16 .. 256}
 const size_t WINO_BPART_BYTES = (size_t)WINO_BIAS_BLOCKS * 256 * 4 * sizeof(float);     // bias partial rows of one phase (4 channels per thread)
 const size_t WINO_L2_BYTES = (size_t)64 * 1024 * sizeof(float);                          // second-level partials: 64 slices x up to 1024 channels
 
-// channels per thread of the transform kernels (ACLGAN_WINO_VEC = 1 | 2 | 4; 2 measured best, profiles/r02_experiments.md)
-int wino_vec() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_WINO_VEC"); v = e ? atoi(e) : 2; if (v != 1 && v != 2 && v != 4) v = 2; }
-    return v;
-}
 // split-bf16 GEMM slices (gemm_bf16x3.hip) for the forward-type products: ACLGAN_WINO_X3=1 / aclgan_set_tuning("wino_x3", 1).  OFF by
 // default: the launch itself is 1.6x faster than the fp32 MFMA slices at fp32 accuracy (ResBlock shape 67.8 against 113 us isolated, 81
 // against 102 us in the step: -8.4 ms of GEMM time per step), but the step does not get faster -- the transform writes 6 instead of 4
 // bytes per value (+3.7 ms), the weight gradient loses the kept fp32 V (+1.6 ms) and, measured on the same box back to back, every
 // OTHER matrix kernel of the step runs 5-8 % slower while these launches are in the mix (the chip is power-limited: the bf16 pipes at
 // full rate cost the clocks of what follows): 121.3 against 119.9 ms of kernel time per step (profiles/r03_experiments.md).
-std::atomic<int> g_wino_x3{-1};
-bool wino_x3() {
-    int v = g_wino_x3.load();
-    if (v < 0) { const char* e = getenv("ACLGAN_WINO_X3"); v = e ? (atoi(e) ? 1 : 0) : 0; g_wino_x3.store(v); }
-    return v == 1;
-}
-// channels per thread of the input transform when it writes the three bf16 planes (ACLGAN_WINO_VEC3)
-int wino_vec3() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ACLGAN_WINO_VEC3"); v = e ? atoi(e) : 2; if (v != 1 && v != 2 && v != 4) v = 2; }
-    return v;
-}
+// Channels per thread of the transform kernels: ACLGAN_WINO_VEC = 1 | 2 | 4 (2 measured best, profiles/r02_experiments.md); ACLGAN_WINO_VEC3 for
+// the input transform when it writes the three bf16 planes
 // planes: 0 = fp32 V; else the element count of one bf16 plane (3-plane output)
 int launch_wino_input(const float* x, float* V, int B, const WViews& vs, int nph, int C, int TY, int TX, int off, int reflect, hipStream_t st, int64_t planes = 0) {
-    const int nv = planes ? wino_vec3() : wino_vec();
+    const int nv = planes ? sw(SW_WINO_VEC3) : sw(SW_WINO_VEC);
     const dim3 grid(grid_for((int64_t)B * TY * TX * (C / nv), 16384), nph);
     if (nv == 4) hipLaunchKernelGGL(wino_input_kernel<4>, grid, dim3(256), 0, st, x, V, B, vs, C, TY, TX, off, reflect, planes);
     else if (nv == 2) hipLaunchKernelGGL(wino_input_kernel<2>, grid, dim3(256), 0, st, x, V, B, vs, C, TY, TX, off, reflect, planes);
@@ -495,7 +468,7 @@ int launch_wino_input(const float* x, float* V, int B, const WViews& vs, int nph
 }
 int launch_wino_output(const float* M, const float* bias, float* y, int B, const WViews& vs, int C, int TY, int TX, int act, int accumulate, int sum,
                        hipStream_t st, float2* stats = nullptr) {
-    const int nv = wino_vec();
+    const int nv = sw(SW_WINO_VEC);
     ACL_REQUIRE((int64_t)B * TY * TX * C < (1ll << 30), "wino_output: plane beyond 2^30 elements");
     const dim3 grid(grid_for((int64_t)B * TY * TX * (C / nv), 16384));
 #define ACL_WO(NV_)                                                                                                                                     \
@@ -512,7 +485,7 @@ int launch_wino_output(const float* M, const float* bias, float* y, int B, const
 }
 // returns the number of bias partial rows PER PHASE written to bpart ([ph][row][C]); C / nv must divide 256
 int launch_wino_outgrad(const float* dy, float* dM, float* bpart, int B, const WViews& vs, int nph, int C, int TY, int TX, hipStream_t st, int* rows) {
-    const int nv = wino_vec(), Cv = C / nv;
+    const int nv = sw(SW_WINO_VEC), Cv = C / nv;
     const int mult = std::max(1, Cv / 256);        // gridDim.x * 256 must be a multiple of Cv
     int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(WINO_BIAS_BLOCKS, cdiv64((int64_t)B * TY * TX * Cv, 256)));
     blocks = cdiv(blocks, mult) * mult;
@@ -537,7 +510,7 @@ int launch_wino_bias_finish(const float* bpart, int rows, int C, float* db, floa
     ACL_CHECK_LAUNCH("wino_bias_finish_kernel");
     return ACLGAN_OK;
 }
-bool wino_bias_ok(int C) { const int Cv = C / wino_vec(); return C % wino_vec() == 0 && (256 % Cv == 0 || Cv % 256 == 0); }
+bool wino_bias_ok(int C) { const int Cv = C / sw(SW_WINO_VEC); return C % sw(SW_WINO_VEC) == 0 && (256 % Cv == 0 || Cv % 256 == 0); }
 
 WViews one_view(const WView& v) { WViews w; w.v[0] = v; w.v[1] = v; w.v[2] = v; w.v[3] = v; w.nph = 1; return w; }
 
@@ -551,13 +524,11 @@ float* take(char*& cur, size_t bytes) { float* p = (float*)cur; cur += align256(
 // ------------------------------------------------------------------------------------------
 // 3x3, stride 1, reflect pad 1, no upsample, 4x4-tileable output, channel counts the GEMM kernel takes, and enough channels to pay
 bool conv_wino_ok(const ConvGeom& g) {
-    return wino_enabled() && g.k == 3 && g.s == 1 && g.p == 1 && g.up == 0 && g.Ho % 4 == 0 && g.Wo % 4 == 0 && g.Ci % 16 == 0 && g.Co % 16 == 0 &&
+    return !sw(SW_NOWINO) && g.k == 3 && g.s == 1 && g.p == 1 && g.up == 0 && g.Ho % 4 == 0 && g.Wo % 4 == 0 && g.Ci % 16 == 0 && g.Co % 16 == 0 &&
            (int64_t)g.Ci * g.Co >= 64 * 64;
 }
 // (U and V slots are sized for the three bf16 planes of the split-bf16 GEMM -- 6 bytes per value -- whether or not it runs; a layer's
 //  cached U is fp32 or planes for the whole update: the choice depends on the layer's shape and the process-wide switch only)
-// tuning / test knob behind aclgan_set_tuning("wino_x3", v); returns the previous value
-int set_wino_x3(int v) { const int old = wino_x3() ? 1 : 0; g_wino_x3.store(v ? 1 : 0); return old; }
 size_t conv_wino_u_bytes(const ConvGeom& g) {
     if (conv_wino_ok(g)) return align256((size_t)36 * g.Co * g.Ci * 6);
     if (conv_up5_wino_ok(g)) return align256((size_t)144 * g.Co * g.Ci * 6);
@@ -583,7 +554,7 @@ int wino_run(int B, int H, int W, int Cin_, int Cout_, const float* in, const fl
         if (fresh_f) { const int rcf = wino_fused_filter(w, Uf, w_co, w_ci, flip, st); if (rcf) return rcf; }
         return wino_fused_launch(B, H, W, Cin_, Cout_, in, Uf, bias, out, act, accumulate, reflect, stats, st);
     }
-    const bool x3 = !keepV && wino_x3() && gemm_x3_shape_ok((int)T, Cin_, Cout_);      // (a kept V feeds the fp32 weight-gradient GEMM: fp32)
+    const bool x3 = !keepV && sw(SW_WINO_X3) && gemm_x3_shape_ok((int)T, Cin_, Cout_);      // (a kept V feeds the fp32 weight-gradient GEMM: fp32)
     const size_t eb = x3 ? 6 : 4;
     float* U = take(cur, (size_t)36 * Cout_ * Cin_ * 6);
     float* V = take(cur, (size_t)36 * T * Cin_ * eb);
@@ -613,7 +584,7 @@ int conv_wino_u_variant(const ConvGeom& g, int dgrad, bool keepV) {
     const int64_t T = (int64_t)g.B * (g.Hi / 4) * (g.Wi / 4);
     if (dgrad) keepV = false;
     if (!keepV && wino_fused_ok(g.B, g.Hi, g.Wi, Cin_, Cout_, act)) return uvar(dgrad, U_FRAG);
-    const bool x3 = !keepV && wino_x3() && gemm_x3_shape_ok((int)T, Cin_, Cout_);
+    const bool x3 = !keepV && sw(SW_WINO_X3) && gemm_x3_shape_ok((int)T, Cin_, Cout_);
     return uvar(dgrad, x3 ? U_X3 : U_PIPE);
 }
 // The transforms of `count` equally shaped 3x3 filters (w0 + i * w_stride floats, OHWI) into U0 + i * u_stride floats, in the layout of
@@ -633,7 +604,7 @@ int conv_wino_prefill(const ConvGeom& g, int uv, const float* w0, int64_t w_stri
 // input transform
 size_t conv_wino_keep_bytes(const ConvGeom& g) {
     if (!conv_wino_ok(g) || g.Co % 64 != 0 || g.Ci % 64 != 0) return 0;
-    if (wino_x3() && gemm_x3_shape_ok(1, g.Ci, g.Co)) return 0;      // the forward writes V as bf16 planes; the fp32 weight-gradient GEMM transforms x itself
+    if (sw(SW_WINO_X3) && gemm_x3_shape_ok(1, g.Ci, g.Co)) return 0;      // the forward writes V as bf16 planes; the fp32 weight-gradient GEMM transforms x itself
     if (wino_fused_ok(g.B, g.Hi, g.Wi, g.Ci, g.Co, g.act)) return 0;         // the fused forward never materialises V
     if (wino_wgrad_fused_ok(g)) return 0;                                    // the fused weight gradient transforms x itself
     return align256((size_t)36 * g.B * (g.Ho / 4) * (g.Wo / 4) * g.Ci * sizeof(float));
@@ -695,7 +666,7 @@ int conv_wgrad_wino(const ConvGeom& g, const float* x, const float* dy, float* d
 // gather kernels (launched by the caller).  ACLGAN_NOWINOUP5=1 keeps the direct phase kernels.
 // ------------------------------------------------------------------------------------------
 bool conv_up5_wino_ok(const ConvGeom& g) {
-    return wino_enabled() && wino_up5_enabled() && g.up == 1 && g.k == 5 && g.p == 2 && g.s == 1 && g.Hi >= 6 && g.Wi >= 6 && g.Ci % 16 == 0 &&
+    return !sw(SW_NOWINO) && !sw(SW_NOWINOUP5) && g.up == 1 && g.k == 5 && g.p == 2 && g.s == 1 && g.Hi >= 6 && g.Wi >= 6 && g.Ci % 16 == 0 &&
            g.Co % 16 == 0 && (int64_t)g.Ci * g.Co >= 64 * 64;
 }
 namespace {
@@ -717,10 +688,10 @@ int conv_up5_wino_u_variant(const ConvGeom& g, int dgrad, bool keepV) {
     const Up5Geo q = up5_geo(g);
     if (!dgrad) {
         if (!keepV && wino_fused_ok(g.B, g.Hi - 2, g.Wi - 2, g.Ci, g.Co, g.act, 4, 1)) return uvar(2, U_FRAG);
-        return uvar(2, (!keepV && wino_x3() && gemm_x3_shape_ok((int)q.T, g.Ci, g.Co)) ? U_X3 : U_PIPE);
+        return uvar(2, (!keepV && sw(SW_WINO_X3) && gemm_x3_shape_ok((int)q.T, g.Ci, g.Co)) ? U_X3 : U_PIPE);
     }
     if (wino_fused_ok(g.B, g.Hi, g.Wi, g.Co, g.Ci, ACLGAN_ACT_NONE, 1, 4)) return uvar(3, U_FRAG);
-    return uvar(3, (wino_x3() && gemm_x3_shape_ok((int)q.Td, g.Co, g.Ci)) ? U_X3 : U_PIPE);
+    return uvar(3, (sw(SW_WINO_X3) && gemm_x3_shape_ok((int)q.Td, g.Co, g.Ci)) ? U_X3 : U_PIPE);
 }
 size_t conv_up5_wino_fwd_scratch_bytes(const ConvGeom& g) {
     if (!conv_up5_wino_ok(g)) return 0;
@@ -729,7 +700,7 @@ size_t conv_up5_wino_fwd_scratch_bytes(const ConvGeom& g) {
 }
 size_t conv_up5_wino_keep_bytes(const ConvGeom& g) {
     if (!conv_up5_wino_ok(g) || g.Co % 64 != 0 || g.Ci % 64 != 0) return 0;
-    if (wino_x3() && gemm_x3_shape_ok(1, g.Ci, g.Co)) return 0;
+    if (sw(SW_WINO_X3) && gemm_x3_shape_ok(1, g.Ci, g.Co)) return 0;
     if (wino_fused_ok(g.B, g.Hi - 2, g.Wi - 2, g.Ci, g.Co, g.act, 4, 1)) return 0;      // the fused forward never materialises V
     return align256((size_t)36 * up5_geo(g).T * g.Ci * sizeof(float));
 }
@@ -744,7 +715,7 @@ int conv_up5_wino_fwd_phases(const ConvGeom& g, const float* x, const float* wp,
         if (fresh_f) { const int rcf = wino_fused_filter(wp, Uf, g.Co, g.Ci, 0, st, 4); if (rcf) return rcf; }
         return wino_fused_up5_fwd(g.B, g.Hi, g.Wi, g.Ci, g.Co, x, Uf, bias, y, g.Ho, g.Wo, g.act, st);
     }
-    const bool x3 = !keepV && wino_x3() && gemm_x3_shape_ok((int)q.T, g.Ci, g.Co);
+    const bool x3 = !keepV && sw(SW_WINO_X3) && gemm_x3_shape_ok((int)q.T, g.Ci, g.Co);
     const size_t eb = x3 ? 6 : 4;
     float* U = take(cur, (size_t)144 * g.Co * g.Ci * 6);
     float* V = take(cur, (size_t)36 * q.T * g.Ci * 6);
@@ -781,7 +752,7 @@ int conv_up5_wino_dgrad_phases(const ConvGeom& g, const float* dy, const float* 
         if (fresh_f) { const int rcf = wino_fused_filter(wp, Uf, g.Co, g.Ci, 1, st, 4); if (rcf) return rcf; }
         return wino_fused_up5_dgrad(g.B, g.Hi, g.Wi, g.Ci, g.Co, dy, Uf, dx, g.Ho, g.Wo, accumulate, st);
     }
-    const bool x3 = wino_x3() && gemm_x3_shape_ok((int)q.Td, g.Co, g.Ci);
+    const bool x3 = sw(SW_WINO_X3) && gemm_x3_shape_ok((int)q.Td, g.Co, g.Ci);
     const size_t eb = x3 ? 6 : 4;
     float* U = take(cur, (size_t)144 * g.Co * g.Ci * 6);
     float* V = take(cur, (size_t)144 * q.Td * g.Co * 6);
@@ -844,17 +815,10 @@ int conv_up5_wino_wgrad_phases(const ConvGeom& g, const float* x, const float* d
 // grid phases writing the parity views of dx); the mirrored halo ring keeps the direct kernel's small launch.  ACLGAN_NOWINOS2=1 keeps the
 // direct kernels; the per-shape decision is wino_fused_s2k4_ok's cost model (aclgan_tuning("wino_fused", 2) takes every eligible shape).
 // ------------------------------------------------------------------------------------------
-// tuning switch "wino_s2k4" (aclgan_tuning; ACLGAN_NOWINOS2=1 sets the default to 0): 0 = the stride-2 layers stay on the direct kernels
-static std::atomic<int> g_wino_s2k4{-1};
-int wino_s2k4_setting() {
-    int v = g_wino_s2k4.load();
-    if (v < 0) { const char* e = getenv("ACLGAN_NOWINOS2"); v = (e && atoi(e)) ? 0 : 1; g_wino_s2k4.store(v); }
-    return v;
-}
-int set_wino_s2k4(int v) { const int old = wino_s2k4_setting(); g_wino_s2k4.store(v ? 1 : 0); return old; }
+// (tuning switch "wino_s2k4"; ACLGAN_NOWINOS2=1 sets its default to 0)
 bool conv_s2k4_wino_ok(const ConvGeom& g, int which) {
-    if (!wino_s2k4_setting() || !wino_enabled() || g.k != 4 || g.s != 2 || g.p != 1 || g.up != 0) return false;
-    if (which == 1 && deterministic()) return false;      // (the ordered ring fold of that mode is wired for the 3x3 layers only)
+    if (!sw(SW_WINO_S2K4) || sw(SW_NOWINO) || g.k != 4 || g.s != 2 || g.p != 1 || g.up != 0) return false;
+    if (which == 1 && sw(SW_DETERMINISTIC)) return false;      // (the ordered ring fold of that mode is wired for the 3x3 layers only)
     return wino_fused_s2k4_ok(g.B, g.Hi, g.Wi, g.Ci, g.Co, which ? ACLGAN_ACT_NONE : g.act, which);
 }
 size_t conv_s2k4_wino_scratch_bytes(const ConvGeom& g) {

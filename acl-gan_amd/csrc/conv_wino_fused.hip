@@ -487,21 +487,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
 }
 
-std::atomic<int> g_wino_fused{-1};
 thread_local int tl_wino_force = 0;      // > 0: this thread's calls take the fused kernel wherever the shape is eligible (the operator entry point)
 
 }  // namespace
 
-// tuning / test knob behind aclgan_set_tuning("wino_fused", v): 0 = the three-launch pipeline of conv_wino.hip, 1 = the fused kernel where its
-// cost model says it pays (wino_fused_ok), 2 = the fused kernel wherever the shape is eligible;
-// returns the previous value.  ACLGAN_WINO_FUSED sets the default.  (bits 4.. select a measurement build when compiled with
-// -DACLGAN_FUSED_ABLATION)
-int wino_fused_mode() {
-    int v = g_wino_fused.load();
-    if (v < 0) { const char* e = getenv("ACLGAN_WINO_FUSED"); v = e ? atoi(e) : 1; if (v < 0 || (v & 15) > 2) v = 1; g_wino_fused.store(v); }
-    return v;
-}
-int set_wino_fused(int v) { const int old = wino_fused_mode(); g_wino_fused.store((v < 0 || (v & 15) > 2) ? 1 : v); return old; }
+// sw(SW_WINO_FUSED) (aclgan_tuning "wino_fused" / ACLGAN_WINO_FUSED): 0 = the three-launch pipeline of conv_wino.hip, 1 = the fused kernel where its
+// cost model says it pays (wino_fused_ok), 2 = the fused kernel wherever the shape is eligible.  (bits 4.. select a measurement build when
+// compiled with -DACLGAN_FUSED_ABLATION)
 // The operator entry point (aclgan_conv3x3_winograd_fused) IS the fused kernel whatever the step's switch says: a per-THREAD override
 // instead of flipping the process-wide switch around the launch (round 4 did; an update running on another thread saw the mode change
 // in the middle of its plan).  Returns the previous value.
@@ -516,7 +508,7 @@ int wino_fused_force(int on) { const int old = tl_wino_force; tl_wino_force = on
 // scales with the tile count: 30 + 0.0488 us per (tile x 256 x 256 channel pair).  Crossover on the 256-channel ResBlock: ~1400 tiles (B = 5.5 at
 // 64 x 64); below it (the reference's own batch_size 3, the 64 x 64 B = 1 launch-floor probe) the pipeline is faster (B = 1: 42 against 93 us).
 bool wino_fused_ok(int B, int H, int W, int Cin_, int Cout_, int act, int gph, int kph) {
-    const int m = tl_wino_force > 0 ? 2 : (wino_fused_mode() & 15);
+    const int m = tl_wino_force > 0 ? 2 : (sw(SW_WINO_FUSED) & 15);
     if (m == 0) return false;
     const bool shape = act != ACLGAN_ACT_TANH && Cin_ % (2 * KC) == 0 && Cout_ % NBC == 0 && (long long)4 * 36 * Cin_ * Cout_ * 4 < 0x7fffffe0ll && H >= 4 && W >= 4 &&
                        (long long)B * (2 * H + 8) * (2 * W + 8) * std::max(Cin_, Cout_) * 4 < 0x7fffffe0ll;
@@ -555,7 +547,7 @@ int wino_fused_go(WfP& p, int ngph, hipStream_t st) {
     p.uphase = 36 * p.Cin * p.Cout * 4;
     p.ubytes = (long long)p.uphase * p.nkph * ngph;
     const dim3 grid(p.ncb * p.ntb, ngph);
-    const int abl = wino_fused_mode() >> 4;
+    const int abl = sw(SW_WINO_FUSED) >> 4;
 #ifdef ACLGAN_FUSED_ABLATION
 #define ACL_ABL(A_) else if (abl == A_) hipLaunchKernelGGL((wino_fused_kernel<A_>), grid, dim3(256), 0, st, p);
     if (abl == 0) hipLaunchKernelGGL(wino_fused_kernel<0>, grid, dim3(256), 0, st, p);
@@ -638,7 +630,7 @@ int wino_fused_filter_s2k4(const float* w, float* Uf, int Co, int Ci, int dgrad,
 // Cost model (microseconds; the fused kernel as in wino_fused_ok, the direct implicit-GEMM kernels at the rates of the round-5 trace:
 // 115 - 145 TFLOP/s on full grids, far less once split-K has to fill the chip) -- mode 1 asks it, mode 2 takes every eligible shape.
 bool wino_fused_s2k4_ok(int B, int Hi, int Wi, int Ci, int Co, int act, int dgrad) {
-    const int m = tl_wino_force > 0 ? 2 : (wino_fused_mode() & 15);
+    const int m = tl_wino_force > 0 ? 2 : (sw(SW_WINO_FUSED) & 15);
     if (m == 0) return false;
     const int Cin_ = dgrad ? Co : Ci, Cout_ = dgrad ? Ci : Co;      // the kernel's K-side / output-side channels
     const bool shape = act != ACLGAN_ACT_TANH && Hi % 2 == 0 && Wi % 2 == 0 && Hi >= 8 && Wi >= 8 && Cin_ % (2 * KC) == 0 && Cout_ % NBC == 0 &&

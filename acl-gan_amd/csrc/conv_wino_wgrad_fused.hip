@@ -413,8 +413,6 @@ __global__ void __launch_bounds__(256) wgrad_fused_finish_kernel(const float* __
     }
 }
 
-std::atomic<int> g_wgrad_fused{-1};
-
 struct WgPlan { int TY, TXS, G, nblk, ks, gper; };
 WgPlan wg_plan(const ConvGeom& g) {
     WgPlan q;
@@ -428,15 +426,6 @@ WgPlan wg_plan(const ConvGeom& g) {
 
 }  // namespace
 
-// tuning / test knob behind aclgan_set_tuning("wino_wgrad_fused", v): 0 = the pipeline of conv_wino.hip, 1 / 2 = the fused kernel wherever the
-// shape is eligible (it pays at every grid size measured); returns the previous value.  ACLGAN_WINO_WGRAD_FUSED sets the default.
-int wino_wgrad_fused_mode() {
-    int v = g_wgrad_fused.load();
-    if (v < 0) { const char* e = getenv("ACLGAN_WINO_WGRAD_FUSED"); v = e ? atoi(e) : 1; if (v < 0 || v > 2) v = 1; g_wgrad_fused.store(v); }
-    return v;
-}
-int set_wino_wgrad_fused(int v) { const int old = wino_wgrad_fused_mode(); g_wgrad_fused.store((v < 0 || v > 2) ? 1 : v); return old; }
-
 // 3x3 stride-1 reflect-pad-1 layers with W a multiple of 16, H of 4, Cout of 64, Cin of 32
 namespace {
 bool wg_shape_ok(const ConvGeom& g) {
@@ -444,8 +433,10 @@ bool wg_shape_ok(const ConvGeom& g) {
            g.B >= 1 && (long long)g.B * g.Hi * g.Wi * std::max(g.Ci, g.Co) * 4 < 0x7fffffe0ll;
 }
 }  // namespace
+// sw(SW_WINO_WGRAD_FUSED) (aclgan_tuning "wino_wgrad_fused" / ACLGAN_WINO_WGRAD_FUSED): 0 = the pipeline of conv_wino.hip, 1 / 2 = the fused
+// kernel wherever the shape is eligible (it pays at every grid size measured)
 bool wino_wgrad_fused_ok(const ConvGeom& g) {
-    const int m = wino_wgrad_fused_mode();
+    const int m = sw(SW_WINO_WGRAD_FUSED);
     if (m == 0) return false;
     const bool shape = wg_shape_ok(g);
     // MEASURED (scripts/probe_wgrad_fused.py, 256 -> 256 channels on 64 x 64 maps, back to back, finish launch included): fused 35 / 46 / 57 / 67 / 91 /

@@ -98,8 +98,7 @@ struct Roctx {
     int (*pop)() = nullptr;
     bool on = false;
     Roctx() {
-        const char* env = getenv("ACLGAN_ROCTX");
-        if (!env || !atoi(env)) return;
+        if (!sw(SW_ROCTX)) return;
         for (const char* name : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"}) {
             void* h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
             if (!h) continue;
@@ -133,11 +132,9 @@ struct StreamPool {
         std::lock_guard<std::mutex> lock(mu);
         if (!s[i]) {
             hipError_t e = hipSuccess;
-            static int prio = -1;      // ACLGAN_SIDE_PRIO=1: the parameter-gradient stream at the highest priority the device offers (measured neutral, round 4)
-            if (prio < 0) { const char* pe = getenv("ACLGAN_SIDE_PRIO"); prio = pe ? atoi(pe) : 0; }
+            const int prio = sw(SW_SIDE_PRIO);      // ACLGAN_SIDE_PRIO=1: the parameter-gradient stream at the highest priority the device offers (measured neutral, round 4)
             // ACLGAN_LANE_PRIO=-1: lanes 1.. at the LOWEST priority (lane 0, the caller's stream, carries the chain everything waits for)
-            static int lprio = -2;
-            if (lprio == -2) { const char* pe = getenv("ACLGAN_LANE_PRIO"); lprio = pe ? atoi(pe) : 0; }
+            const int lprio = sw(SW_LANE_PRIO);
             int lo = 0, hi = 0;
             if (i == 0 && prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) e = hipStreamCreateWithPriority(&s[i], hipStreamNonBlocking, prio > 0 ? hi : lo);
             else if (i > 0 && lprio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) e = hipStreamCreateWithPriority(&s[i], hipStreamNonBlocking, lprio > 0 ? hi : lo);
@@ -228,7 +225,6 @@ struct aclgan_ctx {
     struct UEnt { float* u; bool filled; int layout; int lane, ck; };
     std::map<std::pair<const float*, int>, UEnt> ucache;
     WinoUCache ucache_hook;
-    static bool ucache_enabled() { static int v = -1; if (v < 0) { const char* e = getenv("ACLGAN_NOUCACHE"); v = (e && atoi(e)) ? 0 : 1; } return v == 1; }
     // variant = (0 forward | 1 input gradient | 2 / 3 merged sub-pixel phase filters) | layout << 4 (conv_wino.hip).  An entry remembers the
     // layout it was filled in and the lane that filled it: another layout gets no entry (the caller computes into its scratch -- never a
     // transform read in the wrong order), another lane waits for the filling lane's checkpoint.
@@ -251,7 +247,7 @@ struct aclgan_ctx {
     }
     // make sure the arena holds a slot for the transform of (w, variant); call where an allocation may persist until the update ends
     int ucache_reserve(const float* w, int variant, size_t bytes) {
-        if (!ucache_enabled() || !bytes || ucache.count(std::make_pair(w, variant))) return ACLGAN_OK;
+        if (sw(SW_NOUCACHE) || !bytes || ucache.count(std::make_pair(w, variant))) return ACLGAN_OK;
         float* u = (float*)alloc(bytes);
         if (!u) return ACLGAN_ENOMEM;
         ucache[std::make_pair(w, variant)] = UEnt{u, false, 0, 0, 0};
@@ -259,9 +255,7 @@ struct aclgan_ctx {
     }
     // 16-bit activation / gradient storage of the wide layers (C % 64 == 0) under a 16-bit compute dtype; co16: also the conv outputs
     // that feed a normalisation layer (ACLGAN_ACT16=0 / ACLGAN_CO16=0|1 switch them)
-    bool act16() const { return dtype != ACLGAN_DTYPE_FP32 && act16_enabled(); }
-    static bool act16_enabled() { static int v = -1; if (v < 0) { const char* e = getenv("ACLGAN_ACT16"); v = (e && !atoi(e)) ? 0 : 1; } return v == 1; }
-    static bool co16_enabled() { static int v = -1; if (v < 0) { const char* e = getenv("ACLGAN_CO16"); v = e ? (atoi(e) ? 1 : 0) : 1; } return v == 1; }
+    bool act16() const { return dtype != ACLGAN_DTYPE_FP32 && sw(SW_ACT16); }
 
     // Side stream of the backward (round 3): the weight gradient of a layer depends only on tensors that stay put until the update
     // ends (x, dy, the kept Winograd transform) and nothing in the backward waits for it, while the input gradient is on the critical
@@ -277,7 +271,6 @@ struct aclgan_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool side_pending = false;
     size_t top2 = 0, peak2 = 0;
-    static bool side_enabled() { static int v = -1; if (v < 0) { const char* e = getenv("ACLGAN_SIDE_STREAM"); v = (e && !atoi(e)) ? 0 : 1; } return v == 1; }
     void* alloc2(size_t bytes) {
         const size_t need = top2 + ((bytes + 255) & ~(size_t)255);
         top2 = need;
@@ -347,7 +340,7 @@ struct aclgan_ctx {
     hipStream_t st2_pool = nullptr;
     int lanes_begin(int want) {
         nlanes = std::max(1, std::min(want, (int)MAXL));
-        if (!side_enabled()) nlanes = 1;             // parameter gradients need their own ordered stream once there is more than one lane
+        if (!sw(SW_SIDE_STREAM)) nlanes = 1;             // parameter gradients need their own ordered stream once there is more than one lane
         // Under stream capture (aclgan_Trainer(hip_graph=True): torch.cuda.graph around the update) the whole update, parameter gradients
         // included, runs on the capture stream: the graph is one chain.  Capturing the lanes of the process-wide pool crashed
         // hipStreamEndCapture on this ROCm (round 5, tests/test_gpu_graph.py: gen_update with three pooled lanes), and a graph with a second
@@ -361,8 +354,7 @@ struct aclgan_ctx {
             else (void)hipGetLastError();
         }
         // ACLGAN_CAPTURE_LANES=1 (investigation switch, round 6): capture the pooled lanes as they are
-        static int cap_lanes = -1;
-        if (cap_lanes < 0) { const char* e = getenv("ACLGAN_CAPTURE_LANES"); cap_lanes = (e && atoi(e)) ? 1 : 0; }
+        const int cap_lanes = sw(SW_CAPTURE_LANES);
         const bool cap_one = capturing && !cap_lanes;
         if (cap_one) nlanes = 1;
         cur_lane = 0; st0 = st;
@@ -370,7 +362,7 @@ struct aclgan_ctx {
         ev_next = 0;
         if (dry) return ACLGAN_OK;
         // (parameter-gradient stream first, then the lanes: with the caller's stream that is one hardware queue each up to 3 lanes)
-        if (side_enabled() && !st2_pool) { int rc = aclgan::StreamPool::of_device().get(0, &st2_pool); if (rc) return rc; }
+        if (sw(SW_SIDE_STREAM) && !st2_pool) { int rc = aclgan::StreamPool::of_device().get(0, &st2_pool); if (rc) return rc; }
         st2 = cap_one ? st : st2_pool;
         for (int l = 1; l < nlanes; ++l)
             if (!lane_st[l]) { int rc = aclgan::StreamPool::of_device().get(l, &lane_st[l]); if (rc) return rc; }
@@ -662,13 +654,6 @@ namespace aclgan {
 // graph building blocks.  Every function runs the forward immediately and, when gradients are
 // wanted, pushes one closure on the tape.
 // ------------------------------------------------------------------------------------------
-// arena budget for kept Winograd input transforms (ACLGAN_KEEPV_BUDGET_GB, default 64)
-static size_t keepv_budget() {
-    static size_t v = 0;
-    if (!v) { const char* e = getenv("ACLGAN_KEEPV_BUDGET_GB"); const double gb = e ? atof(e) : 64.0; v = (size_t)(gb * 1073741824.0) + 1; }
-    return v;
-}
-
 // roctx range of one forward pass of a network (ACLGAN_ROCTX=1); closes on every return path
 struct PassScope {
     aclgan_ctx& c; int prev, prev_id;
@@ -721,7 +706,7 @@ static int conv_block(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int Co,
         in = in32;                                // data source of this block; gradients still go to the original (gin)
     }
     const int out_st = (a16 && Co % 64 == 0 && out16) ? dt : 0;
-    const int co_st = has_norm ? ((s_bwd && aclgan_ctx::co16_enabled()) ? dt : 0) : ((f16 || !out_st) ? out_st : 0);
+    const int co_st = has_norm ? ((s_bwd && sw(SW_CO16)) ? dt : 0) : ((f16 || !out_st) ? out_st : 0);
     Act* co = c.new_act(g.B, g.Ho, g.Wo, Co, want_grad, co_st);
     NEED(co->d); if (want_grad) NEED(co->g);
     Act* out = co;
@@ -735,7 +720,7 @@ static int conv_block(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int Co,
         NEED(mean); NEED(rstd);
         // the fused coefficients of the apply stay until the backward: its ReLU mask is then the sign of the same fmaf(x, scale, shift), and
         // neither backward pass reads y (2 of 6 / 1 of 4 tensor reads of the reduce / apply of every activated norm layer)
-        if (want_grad && (act == ACLGAN_ACT_RELU || act == ACLGAN_ACT_LRELU) && norm_mask_setting()) { ss = c.allocf((int64_t)2 * g.B * Co); NEED(ss); }
+        if (want_grad && (act == ACLGAN_ACT_RELU || act == ACLGAN_ACT_LRELU) && sw(SW_NORM_MASK)) { ss = c.allocf((int64_t)2 * g.B * Co); NEED(ss); }
         co->gdt = s_bwd ? dt : 0;             // read by this layer's dgrad / wgrad kernels
     } else if (out_st && !co_st) {            // an fp32-only kernel (image-side first layers) feeding 16-bit consumers: one conversion pass
         out = c.new_act(g.B, g.Ho, g.Wo, Co, want_grad, out_st);
@@ -747,12 +732,12 @@ static int conv_block(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int Co,
     if (gin->need_grad && !s_bwd) gin->gdt = 0;   // this layer's input-gradient kernels write fp32
     // Winograd layers: the forward's input transform V = B^T x B is exactly what the weight gradient needs again -- keep it (persistent
     // until the tape has run: 75 MB per ResBlock convolution at 256x256 B=8, ~6 GB per update) instead of recomputing it
-    // Bounded: the kept transforms of one update may take at most keepv_budget() bytes of the arena (default 64 GB of the 288 GB; 256x256
+    // Bounded: the kept transforms of one update may take at most ACLGAN_KEEPV_BUDGET_GB of the arena (default 64 GB of the 288 GB; 256x256
     // B=8 needs 6.5 GB, 512x512 B=4 13 GB, B=32 26 GB); beyond it a layer's weight gradient recomputes V (same result bit for bit).
     float* keepV = nullptr;
     if (train_w && !f16 && !w16) {
         const size_t kb = conv_fwd_keep_bytes(g);
-        if (kb && c.keep_total + kb <= keepv_budget()) { keepV = (float*)c.alloc(kb); NEED(keepV); c.keep_total += kb; }
+        if (kb && c.keep_total + kb <= (size_t)(sw_real(SW_KEEPV_BUDGET_GB) * 1073741824.0) + 1) { keepV = (float*)c.alloc(kb); NEED(keepV); c.keep_total += kb; }
     }
     const size_t ubytes = f16 ? 0 : conv_wino_u_bytes(g);          // fp32 Winograd layer: its filter transform is cached per update
     if (ubytes && c.ucache_reserve(W.w, g.up ? 2 : 0, ubytes)) { set_error("workspace too small (filter-transform cache)"); return ACLGAN_ENOMEM; }
@@ -809,7 +794,7 @@ static int conv_block(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int Co,
         c.count((es_co + eg_out + eg_co) * (double)co->numel() + ((residual && residual->need_grad) ? (residual->gdt ? 2.0 : 4.0) * (double)co->numel() : 0.0));
         if (train_w) { c.count(es_in * (double)in->numel() + eg_co * (double)co->numel() + 4.0 * ((double)Co * g.K + Co)); c.exec_flops += conv_exec_flops(g, 2, w16); }
         if (gin->need_grad) { c.count(eg_co * (double)co->numel() + es_w * (double)Co * g.K + eg_in * (double)in->numel()); c.exec_flops += conv_exec_flops(g, 1, d16); }
-        const bool side = train_w && aclgan_ctx::side_enabled();      // this layer's weight gradient goes to the side stream
+        const bool side = train_w && sw(SW_SIDE_STREAM);      // this layer's weight gradient goes to the side stream
         if (ubytes && gin->need_grad && !d16 && c.ucache_reserve(W.w, g.up ? 3 : 1, ubytes)) { set_error("workspace too small (filter-transform cache)"); return ACLGAN_ENOMEM; }
         float* g16 = nullptr;
         const size_t mark_pre = c.top;
@@ -893,7 +878,7 @@ static int conv_block(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int Co,
 // before any other lane starts.  Layout and cache key are exactly what the layers will ask for (conv_wino_u_variant); a layer that asks for
 // something else finds no entry and transforms its own filter as before.
 static int prefill_wino_u(aclgan_ctx& c, int net, int B, int H, int W, bool train) {
-    if (!aclgan_ctx::ucache_enabled() || !u_batch_setting()) return ACLGAN_OK;
+    if (sw(SW_NOUCACHE) || !sw(SW_U_BATCH)) return ACLGAN_OK;
     const aclgan_arch& a = c.arch;
     const int nd = a.gen_n_downsample, count = 2 * a.gen_n_res, C = a.gen_dim << nd;
     if (count < 2) return ACLGAN_OK;
@@ -950,8 +935,7 @@ static int prefill_wino_u(aclgan_ctx& c, int net, int B, int H, int W, bool trai
 // previous call's optimizer step wrote the parameters on the caller's stream.
 static int prefill_on_side_lane(aclgan_ctx& c, int B, int H, int W, bool train) {
     const int AB = ACLGAN_NET_GEN_AB, BA = ACLGAN_NET_GEN_BA;
-    static int on_lane = -1;      // ACLGAN_PREFILL_LANE=0: back in lane 0's preamble (A/B switch)
-    if (on_lane < 0) { const char* e = getenv("ACLGAN_PREFILL_LANE"); on_lane = (e && !atoi(e)) ? 0 : 1; }
+    const int on_lane = sw(SW_PREFILL_LANE);      // ACLGAN_PREFILL_LANE=0: back in lane 0's preamble (A/B switch)
     if (c.nlanes <= 1 || !on_lane) { CHK(prefill_wino_u(c, AB, B, H, W, train)); return prefill_wino_u(c, BA, B, H, W, train); }
     const int LP = c.nlanes - 1;
     CHK(c.mark());
@@ -1016,7 +1000,7 @@ static int dense(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int O, int a
             if (in->gw) { tmp = c.allocf((int64_t)B * I); NEED(tmp); dx = tmp; } else dx = in->g;
         }
         // dy *= act'(y), dx on this closure's lane; dw / db (parameter gradients) on the side stream: x and dy stay put until the update ends
-        const bool side = train_w && aclgan_ctx::side_enabled();
+        const bool side = train_w && sw(SW_SIDE_STREAM);
         RUN(linear_bwd(B, I, O, in->d, out->d, out->g, W.w, act, dx, (train_w && !side) ? W.dw : nullptr, (train_w && !side) ? W.db : nullptr, c.st));
         if (side) {
             CHK(c.side_fork());
@@ -1088,7 +1072,7 @@ static int decode(aclgan_ctx& c, int net, bool train, Act* content, Act* style, 
     // (round 6) one launch for the three layers where the widths allow (misc.hip: mlp3_fwd -- the same bits as three linear_fwd launches);
     // activations, accounting and the three backward closures are those of dense()
     const int sdim = style->H * style->W * style->C;
-    const bool fused = mlp_fused_setting() && mlp3_fwd_ok(sdim, a.gen_mlp_dim);
+    const bool fused = sw(SW_MLP_FUSED) && mlp3_fwd_ok(sdim, a.gen_mlp_dim);
     const PW W0 = c.pw(0, net, "mlp.model.0.fc"), W1 = c.pw(0, net, "mlp.model.1.fc"), W2 = c.pw(0, net, "mlp.model.2.fc");
     CHK(dense(c, W0, train, style, a.gen_mlp_dim, ACLGAN_ACT_RELU, &m0, !fused));
     CHK(dense(c, W1, train, m0, a.gen_mlp_dim, ACLGAN_ACT_RELU, &m1, !fused));
@@ -1358,7 +1342,7 @@ static int run_tape_impl(aclgan_ctx& c) {
         if (c.tape[i].pass != last_pass) { if (last_pass != -2) CHK(c.mark()); last_pass = c.tape[i].pass; }
         CHK(c.set_lane(c.tape[i].lane));
         int rc_i = c.tape[i].fn();
-        if (!rc_i && !c.dry && fault_at_setting() >= 0 && (int)(n - 1 - i) == fault_at_setting()) { set_error("injected fault after backward closure %d (tuning key fault_at)", fault_at_setting()); rc_i = ACLGAN_EHIP; }
+        if (!rc_i && !c.dry && sw(SW_FAULT_AT) >= 0 && (int)(n - 1 - i) == sw(SW_FAULT_AT)) { set_error("injected fault after backward closure %d (tuning key fault_at)", sw(SW_FAULT_AT)); rc_i = ACLGAN_EHIP; }
         if (rc_i) { if (marks && open >= 0) Roctx::get().pop(); return rc_i; }
         if (buckets && !done_at[i].empty()) {
             // a bucket handed to the all-reduce must hold everything written into it: the side stream's parameter gradients, and the
@@ -1408,7 +1392,7 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
         hipError_t e = hipMemsetAsync(L, 0, sizeof(float) * (ACLGAN_L_GEN_TOTAL + 1), c.st);
         if (e != hipSuccess) return hip_fail(e, "memset losses");
     }
-    CHK(c.lanes_begin(lanes_setting()));
+    CHK(c.lanes_begin(sw(SW_LANES)));
     CHK(pack_params(c));
     Act *xa, *xb, *z1, *z2, *z3;
     CHK(input_act(c, x_a, B, 3, H, W, &xa));
@@ -1535,7 +1519,7 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
         hipError_t e = hipMemsetAsync(L + ACLGAN_L_DIS_A, 0, sizeof(float) * 4, c.st);
         if (e != hipSuccess) return hip_fail(e, "memset losses");
     }
-    CHK(c.lanes_begin(lanes_setting()));
+    CHK(c.lanes_begin(sw(SW_LANES)));
     CHK(pack_params(c));
     Act *xa, *xb, *z1, *z2, *z3;
     CHK(input_act(c, x_a, B, 3, H, W, &xa));
@@ -1634,8 +1618,8 @@ int aclgan_ctx_enable_capture(aclgan_ctx* ctx) {
 int aclgan_warm_streams(int lanes) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return ACLGAN_OK; }
-    if (!aclgan_ctx::side_enabled()) return ACLGAN_OK;
-    lanes = std::max(1, std::min(lanes <= 0 ? lanes_setting() : lanes, 3));
+    if (!sw(SW_SIDE_STREAM)) return ACLGAN_OK;
+    lanes = std::max(1, std::min(lanes <= 0 ? sw(SW_LANES) : lanes, 3));
     hipStream_t s = nullptr;
     int rc = aclgan::StreamPool::of_device().get(0, &s);
     for (int l = 1; l < lanes && rc == ACLGAN_OK; ++l) rc = aclgan::StreamPool::of_device().get(l, &s);
@@ -1829,7 +1813,7 @@ static int step_common(aclgan_ctx* ctx, const float* x_a, const float* x_b, cons
     // the bound workspace against this update's need (a dry run, cached per shape / dtype / switch setting): an undersized workspace is
     // refused here, before anything is enqueued (the allocator checks every request as well)
     if (check_shape(*ctx, B, H, W) == ACLGAN_OK) {
-        const aclgan_ctx::NeedKey key{group_trained, B, H, W, ctx->dtype, tuning_epoch(), deterministic() ? 1 : 0, ctx->bucket_elems > 0 ? 1 : 0};
+        const aclgan_ctx::NeedKey key{group_trained, B, H, W, ctx->dtype, tuning_epoch(), sw(SW_DETERMINISTIC), ctx->bucket_elems > 0 ? 1 : 0};
         auto it = ctx->need_cache.find(key);
         if (it == ctx->need_cache.end()) {
             size_t need = 0;

@@ -474,7 +474,7 @@ int linear_bwd(int B, int I, int O, const float* x, const float* y, float* dy, c
         ACL_CHECK_LAUNCH("linear_dw_kernel");
     }
     if (dx) {
-        int slices = (O >= 512 && !deterministic()) ? std::min(64, O / 64) : 1;     // O-slices combine with fp32 atomics: one slice in deterministic mode
+        int slices = (O >= 512 && !sw(SW_DETERMINISTIC)) ? std::min(64, O / 64) : 1;     // O-slices combine with fp32 atomics: one slice in deterministic mode
         const int oslice = cdiv(O, slices);
         slices = cdiv(O, oslice);
         if (slices > 1) { rc = fill_zero(dx, (int64_t)B * I, st); if (rc) return rc; }
@@ -768,7 +768,7 @@ __global__ void __launch_bounds__(256) l1_finish_kernel(const float* __restrict_
 int l1_loss(const float* a, int a_stride, const float* b, int64_t npix, float* loss_slot, float* d_a, float gscale, int d_accumulate, hipStream_t st,
             const float* lscale, float* part) {
     int blocks = (int)std::min<int64_t>(cdiv64(npix, 256), L1_PART_FLOATS);
-    if (!part && deterministic()) blocks = 1;
+    if (!part && sw(SW_DETERMINISTIC)) blocks = 1;
     hipLaunchKernelGGL(l1_kernel, dim3(blocks), dim3(256), 0, st, a, a_stride, b, npix, loss_slot, d_a, gscale, d_accumulate, lscale, part);
     ACL_CHECK_LAUNCH("l1_kernel");
     if (part) {

@@ -335,8 +335,9 @@ int aclgan_conv2d_wgrad16(const aclgan_conv_desc* d, int dtype, const float* x, 
 int aclgan_conv16s_ok(const aclgan_conv_desc* d, int which);
 /* forward on 16-bit x (NHWC) and the OHWI weight pack: y (storage y_storage) = act(conv(x16) + bias) */
 int aclgan_conv2d_fwd16s(const aclgan_conv_desc* d, int dtype, const void* x16, const void* w16, const float* bias, void* y, int y_storage, void* stream);
-/* Process-wide tuning knobs that also exist as environment variables, settable at run time (tests use this to run every tile shape of
- * csrc/conv_glds16.hip).  key "glds_tile": 0 / 1 = 128-row tiles (default), 2 = 256 x 128, 3 = 256 x 256 where the shape allows, 4 = the
+/* Process-wide switches (csrc/switches.hip; every key, its environment variable, default and accepted values: DESIGN.md section 6).
+ * Twelve of them are settable at run time (tests use this to run every tile shape of csrc/conv_glds16.hip); the value is normalised as
+ * the environment variable's would be.  key "glds_tile": 0 / 1 = 128-row tiles (default), 2 = 256 x 128, 3 = 256 x 256 where the shape allows, 4 = the
  * largest tile that still fills the chip.  key "wino_x3": 1 = the GEMM slices of the fp32 Winograd pipeline run as split-bf16
  * products on the bf16 matrix cores (fp32-accurate, see aclgan_gemm_slices_x3), 0 (default) = on the fp32 MFMA kernel.
  * key "dgrad16s_direct": 1 = aclgan_conv2d_dgrad16s stores pixels without mirrored partners straight into a 16-bit dx (bit-identical,
@@ -361,15 +362,17 @@ int aclgan_conv2d_fwd16s(const aclgan_conv_desc* d, int dtype, const void* x16, 
  * generator's MLP forward (networks.py:280-292) is one launch (aclgan_mlp3_fwd), 0 = three aclgan_linear_fwd launches; the same bits either way.
  * key "fault_at" (test hook; -1 = off): the backward replay of the next updates fails with ACLGAN_EHIP after that many
  * closures have been enqueued -- exercises the error path (all internal streams drained before the call returns).
- * Returns the previous value, -1 for an unknown key.  The switches are atomics (a concurrent update sees the old or the new value, never a
+ * Returns the previous value, -1 for an unknown or read-only key.  The switches are atomics (a concurrent update sees the old or the new value, never a
  * torn one), but changing one WHILE an update is being enqueued changes that update's plan half way: do not. */
 int aclgan_set_tuning(const char* key, int value);
 /* The same switches with the status in the return value (round 5): ACLGAN_OK and the previous setting through *previous (may be NULL), or
- * ACLGAN_EINVAL for an unknown key (aclgan_set_tuning cannot tell -1 "unknown" from a previous value). */
+ * ACLGAN_EINVAL for an unknown key or one that only its environment variable sets (aclgan_set_tuning cannot tell -1 "unknown" from a
+ * previous value).  Every successful call bumps the tuning epoch. */
 int aclgan_tuning(const char* key, int value, int* previous);
-/* Read a switch without touching it (round 6; no state change, no tuning-epoch bump): keys "lanes", "u_batch", "norm_mask", "mlp_fused", "wino_fused",
- * "wino_wgrad_fused", "wino_s2k4", "fault_at", and "epoch" = the number of aclgan_tuning calls so far (cached switch-dependent results -- an arena
- * size -- are valid for one epoch).  ACLGAN_EINVAL for any other key. */
+/* Read a switch without changing it (round 6; no tuning-epoch bump): every key of the table -- the twelve settable ones and the
+ * environment-only switches under the variable's name without ACLGAN_, lower-cased ("nowino", "wino_vec", "deterministic", ...; a switch
+ * not read before is latched from its environment now) -- and "epoch" = the number of aclgan_tuning calls so far (cached switch-dependent
+ * results -- an arena size -- are valid for one epoch).  ACLGAN_EINVAL for any other key. */
 int aclgan_tuning_get(const char* key, long long* value);
 /* The same launch with the normalisation statistics taken from its epilogue (round 3; replaces the norm_stats pass over y that
  * follows the conv in reference networks.py:382-395 Conv2dBlock.forward -> self.norm).  aclgan_conv2d_fwd16s_stats_chunk = rows R per
