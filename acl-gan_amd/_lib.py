@@ -132,6 +132,10 @@ SIGNATURES = {
     "aclgan_cast_storage": (ci, [vp, ci, vp, ci, i64, vp]),
     "aclgan_norm_fwd_st": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.POINTER(ci), vp]),
     "aclgan_norm_bwd_st": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, C.POINTER(ci), vp]),
+    "aclgan_conv2d_fwd16_x16_st": (ci, [C.POINTER(ConvDesc), ci, vp, vp, vp, vp, vp, ci, vp, vp]),
+    "aclgan_norm_fwd_x": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, C.POINTER(ci), vp, vp]),
+    "aclgan_norm_bwd_x": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, C.POINTER(ci), vp, vp, vp]),
+    "aclgan_norm_bwd_ln_params": (ci, [vp, ci, ci, vp, vp, vp]),
     "aclgan_conv2d_fwd16_scratch_bytes": (sz, [C.POINTER(ConvDesc)]),
     "aclgan_conv2d_dgrad16_scratch_bytes": (sz, [C.POINTER(ConvDesc)]),
     "aclgan_conv2d_wgrad16_scratch_bytes": (sz, [C.POINTER(ConvDesc)]),

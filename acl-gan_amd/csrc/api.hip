@@ -69,7 +69,9 @@ int aclgan_conv3x3_winograd_fused(const float* x, const float* Uf, const float* 
                                   int accumulate, float* stats, void* stream) {
     ACL_REQUIRE(x && Uf && y && B > 0, "conv3x3_winograd_fused: null argument");
     const int old = wino_fused_force(1);      // (the entry point IS the fused kernel, whatever the step's switch and cost model say: per thread)
-    const int rc = wino_fused_launch(B, H, W, Cin, Cout, x, Uf, bias, y, act, accumulate, reflect, (float2*)stats, (hipStream_t)stream);
+    // (the launcher's padding flag is a tri-state -- 2 is the edge replication of wino_fused_s2k4_fwd, internal to the stride-2 path; this
+    //  entry point documents reflect != 0 as reflection padding, so every non-zero value is normalised to 1)
+    const int rc = wino_fused_launch(B, H, W, Cin, Cout, x, Uf, bias, y, act, accumulate, reflect ? 1 : 0, (float2*)stats, (hipStream_t)stream);
     wino_fused_force(old);
     if (rc == ACLGAN_EUNSUPPORTED) set_error("conv3x3_winograd_fused: shape not eligible (H, W multiples of 4, Cin of 16, Cout of 64, no tanh)");
     return rc;
@@ -203,6 +205,18 @@ int aclgan_conv2d_fwd16_x16(const aclgan_conv_desc* d, int dtype, const void* x1
     if (rc == ACLGAN_EUNSUPPORTED) set_error("conv2d_fwd16_x16: no 16-bit kernel for this shape (Cin, Cout must be multiples of 32)");
     return rc;
 }
+// the same with y stored in the compute dtype (y_storage = dtype) as the step writes the output of a wide layer without normalisation
+int aclgan_conv2d_fwd16_x16_st(const aclgan_conv_desc* d, int dtype, const void* x16, const float* w, const void* w16, const float* bias, void* y,
+                               int y_storage, void* scratch, void* stream) {
+    ConvGeom g;
+    int rc = make_geom(d, &g);
+    if (rc) return rc;
+    ACL_REQUIRE(x16 && w16 && y, "conv2d_fwd16_x16_st: null buffer");
+    ACL_REQUIRE(y_storage == 0 || y_storage == dtype, "conv2d_fwd16_x16_st: y storage must be fp32 or the compute dtype");
+    rc = conv_fwd16(g, dtype, nullptr, w, w16, bias, (float*)y, scratch, (hipStream_t)stream, x16, y_storage);
+    if (rc == ACLGAN_EUNSUPPORTED) set_error("conv2d_fwd16_x16_st: no 16-bit kernel for this shape (Cin, Cout must be multiples of 32)");
+    return rc;
+}
 int aclgan_conv2d_dgrad16(const aclgan_conv_desc* d, int dtype, const float* dy, const float* w, const void* w16t, float* dx, int accumulate,
                           void* scratch, void* stream) {
     ConvGeom g;
@@ -289,6 +303,33 @@ int aclgan_norm_bwd_st(int kind, int act, int B, int HW, int C, const void* x, c
     NormST s;
     s.x = storage[0]; s.y = storage[1]; s.dy = storage[2]; s.dx = storage[3]; s.dres = storage[4];
     return norm_bwd(kind, act, B, HW, C, x, y, dy, w, w_stride, mean, rstd, dx, dw, db, dres, dres_accumulate, scratch, (hipStream_t)stream, &s);
+}
+
+// the step's own variants of the two normalisation calls (engine.hip conv_block): statistics from a conv epilogue, storage codes, the fused
+// scale / shift kept from the forward for the backward's activation mask, and the LayerNorm gamma / beta totals deferred to a later launch
+int aclgan_norm_fwd_x(int kind, int act, int B, int HW, int C, const void* x, const float* w, const float* b, int w_stride, const void* residual,
+                      void* y, float* mean, float* rstd, void* scratch, const float* stats, int stats_chunk, const int* storage, float* ss_out,
+                      void* stream) {
+    ACL_REQUIRE(x && y && mean && rstd && scratch, "norm_fwd_x: null buffer");
+    NormST s;
+    if (storage) { s.x = storage[0]; s.y = storage[1]; s.res = storage[2]; }
+    return norm_fwd(kind, act, B, HW, C, x, w, b, w_stride, residual, y, mean, rstd, scratch, (hipStream_t)stream, stats, stats_chunk, &s, ss_out);
+}
+int aclgan_norm_bwd_x(int kind, int act, int B, int HW, int C, const void* x, const void* y, const void* dy, const float* w, int w_stride,
+                      const float* mean, const float* rstd, void* dx, float* dw, float* db, void* dres, int dres_accumulate, void* scratch,
+                      const int* storage, const float* ss, float* sbc_out, void* stream) {
+    ACL_REQUIRE(x && dy && mean && rstd && dx && scratch, "norm_bwd_x: null buffer");
+    ACL_REQUIRE(y || act == ACLGAN_ACT_NONE || (ss && (act == ACLGAN_ACT_RELU || act == ACLGAN_ACT_LRELU)),
+                "norm_bwd_x: an activation needs y (ss replaces it for ReLU / LeakyReLU only)");
+    ACL_REQUIRE(!sbc_out || kind == ACLGAN_NORM_LN, "norm_bwd_x: sbc_out is for the LayerNorm only");
+    NormST s;
+    if (storage) { s.x = storage[0]; s.y = storage[1]; s.dy = storage[2]; s.dx = storage[3]; s.dres = storage[4]; }
+    return norm_bwd(kind, act, B, HW, C, x, y, dy, w, w_stride, mean, rstd, dx, dw, db, dres, dres_accumulate, scratch, (hipStream_t)stream, &s,
+                    sbc_out, ss);
+}
+int aclgan_norm_bwd_ln_params(const float* sbc, int B, int C, float* dgamma, float* dbeta, void* stream) {
+    ACL_REQUIRE(sbc && B > 0 && C > 0, "norm_bwd_ln_params: bad arguments");
+    return norm_bwd_ln_params(sbc, B, C, dgamma, dbeta, (hipStream_t)stream);
 }
 
 int aclgan_linear_fwd(int B, int I, int O, const float* x, const float* w, const float* bias, int act, float* y, void* stream) {

@@ -398,6 +398,25 @@ int aclgan_norm_fwd_st(int kind, int act, int B, int HW, int C, const void* x, c
 int aclgan_norm_bwd_st(int kind, int act, int B, int HW, int C, const void* x, const void* y, const void* dy, const float* w, int w_stride,
                        const float* mean, const float* rstd, void* dx, float* dw, float* db, void* dres, int dres_accumulate, void* scratch,
                        const int* storage, void* stream);
+/* aclgan_conv2d_fwd16_x16 with y stored in the compute dtype when y_storage == dtype (the output rounded once), as the training step writes
+ * the output of a wide layer without normalisation */
+int aclgan_conv2d_fwd16_x16_st(const aclgan_conv_desc* d, int dtype, const void* x16, const float* w, const void* w16, const float* bias, void* y,
+                               int y_storage, void* scratch, void* stream);
+/* aclgan_norm_fwd_st / aclgan_norm_bwd_st with the operands the training step passes internally:
+ * stats / stats_chunk: (mean, M2) partials of groups of stats_chunk pixels, [B][HW / stats_chunk][C], as a conv epilogue emits them
+ *   (aclgan_conv2d_fwd16s_stats with aclgan_conv2d_fwd16s_stats_chunk); NULL / 0: the separate statistics pass;
+ * storage (NULL: all fp32): {x, y, residual} / {x, y, dy, dx, dres};
+ * ss_out (optional, 2 B C floats): the fused coefficients (scale | shift) of y = act(x * scale + shift); passed back to the backward as ss,
+ *   a ReLU / LeakyReLU mask is recovered from x and ss (y is then not read and may be NULL);
+ * sbc_out (optional, LayerNorm only, [B][C][2] floats): the per-sample totals (sum g, sum g * xhat) instead of the gamma / beta gradients;
+ *   aclgan_norm_bwd_ln_params then adds them: dgamma[c] += sum_b sbc[b][c][1], dbeta[c] += sum_b sbc[b][c][0]. */
+int aclgan_norm_fwd_x(int kind, int act, int B, int HW, int C, const void* x, const float* w, const float* b, int w_stride, const void* residual,
+                      void* y, float* mean, float* rstd, void* scratch, const float* stats, int stats_chunk, const int* storage, float* ss_out,
+                      void* stream);
+int aclgan_norm_bwd_x(int kind, int act, int B, int HW, int C, const void* x, const void* y, const void* dy, const float* w, int w_stride,
+                      const float* mean, const float* rstd, void* dx, float* dw, float* db, void* dres, int dres_accumulate, void* scratch,
+                      const int* storage, const float* ss, float* sbc_out, void* stream);
+int aclgan_norm_bwd_ln_params(const float* sbc, int B, int C, float* dgamma, float* dbeta, void* stream);
 size_t aclgan_conv2d_fwd16_scratch_bytes(const aclgan_conv_desc* d);
 size_t aclgan_conv2d_dgrad16_scratch_bytes(const aclgan_conv_desc* d);
 size_t aclgan_conv2d_wgrad16_scratch_bytes(const aclgan_conv_desc* d);

@@ -24,6 +24,10 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(L.SIGNATURES.keys()), declared ^ set(L.SIGNATURES.keys())
     for name in declared:
         assert getattr(L.lib, name) is not None
+    # and the binding passes as many arguments as the header declares
+    for name, args in re.findall(r"\b(aclgan_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", hdr):
+        n = 0 if args.strip() in ("", "void") else args.count(",") + 1
+        assert n == len(L.SIGNATURES[name][1]), (name, n, len(L.SIGNATURES[name][1]))
     assert L.lib.aclgan_version() >= 100
 
 

@@ -159,6 +159,16 @@ def test_winograd_fused_kernel(L, case):
         assert out[2][3] < out[0][3], "the forced mode did not take the fused kernel (launch counts %d vs %d)" % (out[2][3], out[0][3])
     # same arithmetic, different summation order
     assert rel_err(out[2][0], out[0][0]) < 5e-5 and rel_err(out[2][1], out[0][1]) < 5e-5
+    if k == 3 and up == 0 and Hi % 4 == 0 and Wi % 4 == 0 and Ci % 16 == 0 and Co % 64 == 0:
+        # the entry point itself (include/aclgan_hip.h: "reflect != 0: reflection padding") with any non-zero flag -- the launcher's
+        # internal edge mode (2) and a negative value included -- pads by reflection
+        Uf = torch.empty(36 * Co * Ci, device="cuda")
+        L.check(L.lib.aclgan_winograd_filter_frag(L.ptr(wg), L.ptr(Uf), Co, Ci, 0, L.stream_ptr()), "winograd_filter_frag")
+        for flag in (1, 2, -1):
+            y = torch.full((B, Hi, Wi, Co), float("nan"), device="cuda")
+            L.check(L.lib.aclgan_conv3x3_winograd_fused(L.ptr(xg), L.ptr(Uf), L.ptr(bg), L.ptr(y), B, Hi, Wi, Ci, Co, L.ACT[act], flag, 0, None,
+                                                        L.stream_ptr()), "conv3x3_winograd_fused")
+            assert rel_err(nchw(y), ref) < TOL, (flag, rel_err(nchw(y), ref))
 
 
 S2K4_CASES = [
