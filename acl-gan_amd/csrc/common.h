@@ -195,6 +195,7 @@ int conv_fwd_small(const ConvGeom& g, const float* x, const float* w, const floa
 int conv_wgrad_small(const ConvGeom& g, const float* x, const float* dy, float* dw, float* db, hipStream_t st, void* scratch = nullptr);
 size_t conv_wgrad_small_scratch_bytes(const ConvGeom& g);
 int conv_dgrad_small(const ConvGeom& g, const float* dy, const float* w, float* dxp, hipStream_t st);
+bool conv_s2k4_thin_dgrad_ok(const ConvGeom& g);      // conv_dgrad_small takes this layer onto its VALU stride-2 kernel
 
 size_t norm_scratch_bytes(int B, int HW, int C);
 // storage codes (st16.h: 0 fp32, ACLGAN_DTYPE_BF16, ACLGAN_DTYPE_FP16) of the tensors a normalisation call touches; statistics,

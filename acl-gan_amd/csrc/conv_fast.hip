@@ -1312,14 +1312,19 @@ double conv_exec_flops(const ConvGeom& g, int which, bool f16) {
         if (wgrad_kc_ok(g) && conv_wgrad_wino_scratch_bytes(g)) return pipe_flops(g.B, g.Hi, g.Wi, g.Ci, g.Co, 1);
         return direct;
     }
-    if (!f16 && !sw(SW_NOFAST) && which < 2 && conv_s2k4_wino_ok(g, which)) {
+    // (the input gradient's phases run only where dgrad_fast_all writes the interior straight into dx: not under ACLGAN_NODIRECT, and not
+    //  when the opt-in merged interior + halo launch (ACLGAN_MERGEDHALO) takes the layer first)
+    const bool s2k4_dg_direct = !sw(SW_NODIRECT) && !sw(SW_MERGEDHALO);
+    if (!f16 && !sw(SW_NOFAST) && which < 2 && conv_s2k4_wino_ok(g, which) && (which == 0 || s2k4_dg_direct)) {
         if (which == 0) return fused_flops(g.B, g.Ho, g.Wo, g.Ci, g.Co, 1, 4);
         const double halo = 2.0 * g.B * ((double)g.Hp * g.Wp - (double)g.Hi * g.Wi) * g.Ci * g.Co * 2.0;      // 2 of the 4 taps of a parity class per ring position
         return fused_flops(g.B, g.Ho, g.Wo, g.Co, g.Ci, 4, 1) + halo;
     }
-    // direct kernels: whole tiles along the narrow dimension.  The input gradient of an image-side layer (Cin 3 / 6: the first discriminator
-    // layers) runs on 32-column tiles -- 32 / Cin times the necessary FLOPs; the thin-channel weight gradients (conv_small.hip, 4x4x1 MFMA
-    // blocks of 4 thin channels, 7 filter rows per workgroup) measured 1.09 x (Cout 4) and 1.09 x 4 / 3 (Cin 3) of theirs (SQ_INSTS_MFMA, round 6)
+    // the input gradient of the first discriminator layers (4x4 stride 2, Cin 3 / 6) runs on conv_s2k4_thin_dgrad_kernel: VALU only, no MFMA
+    if (which == 1 && !f16 && conv_s2k4_thin_dgrad_ok(g)) return 0.0;
+    // direct kernels: whole tiles along the narrow dimension.  The input gradient of any other image-side layer (Cin < 32) runs on 32-column
+    // tiles -- 32 / Cin times the necessary FLOPs; the thin-channel weight gradients (conv_small.hip, 4x4x1 MFMA blocks of 4 thin channels,
+    // 7 filter rows per workgroup) measured 1.09 x (Cout 4) and 1.09 x 4 / 3 (Cin 3) of theirs (SQ_INSTS_MFMA, round 6)
     if (which == 1 && g.Ci < 32) return direct * 32.0 / g.Ci;
     if (which == 2 && g.k == 7 && (g.Ci < 16 || g.Co < 16)) return direct * 1.09 * (g.Ci == 3 ? 4.0 / 3.0 : 1.0);
     return direct;

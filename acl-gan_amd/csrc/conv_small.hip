@@ -737,10 +737,14 @@ int conv_fwd_small(const ConvGeom& g, const float* x, const float* w, const floa
 }
 
 // dgrad of a thin-input 7x7 layer onto the padded grid dxp [B][H+6][W+6][Ci] (the caller folds the reflection)
+// the first discriminator layers (4x4 stride 2 pad 1, Cin 3 / 6): input gradient on the VALU kernel below (also conv_exec_flops' predicate)
+bool conv_s2k4_thin_dgrad_ok(const ConvGeom& g) {
+    return !sw(SW_NOSMALL) && !sw(SW_NOTHIN) && sw(SW_THININ2) && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && (g.Ci == 3 || g.Ci == 6) && g.Co % 4 == 0 &&
+           g.Hi % 2 == 0 && g.Wi % 2 == 0;
+}
 int conv_dgrad_small(const ConvGeom& g, const float* dy, const float* w, float* dxp, hipStream_t st) {
     // round 6: ... and of the first discriminator layers (4x4 stride 2 pad 1) onto [B][H+2][W+2][Ci]
-    if (!sw(SW_NOSMALL) && !sw(SW_NOTHIN) && sw(SW_THININ2) && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && (g.Ci == 3 || g.Ci == 6) && g.Co % 4 == 0 &&
-        g.Hi % 2 == 0 && g.Wi % 2 == 0) {
+    if (conv_s2k4_thin_dgrad_ok(g)) {
         const int64_t nthr = (int64_t)g.B * ((g.Hp + 1) / 2) * ((g.Wp + 1) / 2);
         const dim3 grid((unsigned)cdiv64(nthr, 256));
         if (g.Ci == 3) hipLaunchKernelGGL(conv_s2k4_thin_dgrad_kernel<3>, grid, dim3(256), 0, st, dy, w, dxp, g.B, g.Ho, g.Wo, g.Co, g.Hp, g.Wp);

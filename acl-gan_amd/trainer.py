@@ -385,11 +385,12 @@ class aclgan_Trainer:
         forward: inference must not inherit the training step's shape constraints or its arena size)."""
         key = (B, H, W)
         have = self._ws_shape
-        # (an update's need depends on the library's tuning switches -- lanes, batched transforms, kernel choices: the cached size is
-        #  valid for one tuning epoch; after aclgan_tuning the next call sizes and binds again instead of failing with ACLGAN_ENOMEM)
+        # (an update's need depends on the library's tuning switches -- lanes, batched transforms, kernel choices -- and so does a
+        #  forward's: the 4x4 stride-2 Winograd scratch follows wino_fused / wino_s2k4.  The cached size is valid for one tuning epoch;
+        #  after aclgan_tuning the next call sizes and binds again instead of failing with ACLGAN_ENOMEM)
         ep = C.c_longlong()
         L.check(L.lib.aclgan_tuning_get(b"epoch", C.byref(ep)), "tuning_get")
-        if have is not None and have[0] >= B and have[1:3] == (H, W) and (forward_only or (have[3] and have[4] == ep.value)):
+        if have is not None and have[0] >= B and have[1:3] == (H, W) and have[4] == ep.value and (forward_only or have[3]):
             return
         need = C.c_size_t()
         if forward_only:

@@ -188,19 +188,21 @@ def test_step_reproducible_bit_for_bit(L, dtype):
 _ORACLE_CACHE = {}
 
 
-def chained_report(seed, steps=3):
-    """three chained (dis_update, gen_update, update_learning_rate) iterations of the deterministic HIP trainer and of the fp32 oracle
-    from one state: per network (max |dp| / lr, share of elements within 0.05 lr, relative L2 error of the update p - p0), plus the trainer"""
+def chained_report(seed, steps=3, B=2, S=64, full_width=False):
+    """`steps` chained (dis_update, gen_update, update_learning_rate) iterations of the deterministic HIP trainer and of the fp32 oracle
+    from one state: per network (max |dp| / lr, share of elements within 0.05 lr, relative L2 error of the update p - p0), plus the trainer.
+    Fixture: B images of S x S, the reduced-width network (dim 16, 2 ResBlocks) unless full_width (the configuration's own widths)."""
     from aclgan_amd.trainer import aclgan_Trainer
     cfg = O.default_config()
-    cfg["gen"].update(dim=16, mlp_dim=32, n_res=2); cfg["dis"].update(dim=16)
+    if not full_width:
+        cfg["gen"].update(dim=16, mlp_dim=32, n_res=2); cfg["dis"].update(dim=16)
     cfg["display_size"] = 1
     cfg["focus_epsilon"] = 0.5
     nets = O.test_nets(cfg, seed)
     g = torch.Generator().manual_seed(71 + seed)
-    x_a = torch.rand(2, 3, 64, 64, generator=g) * 2 - 1
-    x_b = torch.rand(2, 3, 64, 64, generator=g) * 2 - 1
-    zs = [[torch.randn(2, 8, 1, 1, generator=g) for _ in range(6)] for _ in range(steps)]
+    x_a = torch.rand(B, 3, S, S, generator=g) * 2 - 1
+    x_b = torch.rand(B, 3, S, S, generator=g) * 2 - 1
+    zs = [[torch.randn(B, 8, 1, 1, generator=g) for _ in range(6)] for _ in range(steps)]
 
     def run():
         tr = aclgan_Trainer(cfg, deterministic=True)
@@ -212,12 +214,13 @@ def chained_report(seed, steps=3):
         return tr
     tr = run()
     p0 = {n: {k: v.clone() for k, v in nets[n].items()} for n in O.OracleTrainer.NETS}
-    if (seed, steps) not in _ORACLE_CACHE:      # (the oracle's three CPU steps are the slow part: shared by the convolution paths)
+    key = (seed, steps, B, S, full_width)
+    if key not in _ORACLE_CACHE:      # (the oracle's chained CPU steps are the slow part: shared by the convolution paths)
         orc = O.OracleTrainer(cfg, nets=nets)
         for it in range(steps):
             orc.dis_update(x_a, x_b, zs[it][:3]); orc.gen_update(x_a, x_b, zs[it][3:]); orc.update_learning_rate()
-        _ORACLE_CACHE[(seed, steps)] = orc
-    orc = _ORACLE_CACHE[(seed, steps)]
+        _ORACLE_CACHE[key] = orc
+    orc = _ORACLE_CACHE[key]
     lr = cfg["lr"]
     report = {}
     for n in O.OracleTrainer.NETS:
@@ -304,3 +307,74 @@ def test_three_chained_steps_parameters_match_oracle_elementwise(L, det, fused):
 # drawn by the rounding pattern, not by the path.  Bounds = those means with ~7 % (shares) / ~2x (errors) of room.
 CHAIN_BOUNDS = {"gen_share": 0.80, "dis_share": 0.999, "gen_update": 0.06, "dis_update": 2.5e-3, "share_gap": 0.06, "err_ratio": 2.0, "err_floor": 2e-3}
 CHAIN_MEANS = {}
+
+
+# 256x256 B=3 full width (configs/male2female.yaml: the reference's own configuration), two chained iterations.  One fixture: its oracle chain
+# is 4 full-width CPU updates.  Measured on the MI355X (seed 6), stride-2 phases on / off -- (max |dp| / lr, share within 0.05 lr, update error):
+#   gen_AB 4.03 / 4.01, 0.913 / 0.914, 5.29e-2 / 5.22e-2;  gen_BA 3.94 / 3.99, 0.938 / 0.943, 4.31e-2 / 4.00e-2;
+#   dis_A 0.25 / 0.24, 1.0000 / 1.0000, 1.11e-4 / 1.00e-4;  dis_2 1.93 / 1.93, 0.9998 / 0.9998, 1.5e-3 / 1.5e-3.
+# (ii) holds them to CHAIN_BOUNDS' share_gap / err_ratio / err_floor, the rule the fused 3x3 path is held to above.
+S2_CHAIN_SEEDS = (6,)
+
+
+def adam_elementwise_bound(beta1, beta2, steps):
+    """the largest |p_HIP - p_oracle| / lr two Adam runs from one state can reach after `steps` updates, whatever their gradients: each step
+    moves an element by lr |m_hat| / (sqrt(v_hat) + eps), and over all gradient histories max |m_hat| / sqrt(v_hat) at step t is
+    (1 - b1) / (1 - b1^t) / sqrt((1 - b2) / (1 - b2^t)) * sqrt(sum_j b1^2j / b2^j) (Cauchy-Schwarz): 1 at step 1, 1.054 at step 2 for the
+    configuration's (0.5, 0.999) -- "2 lr per step" only holds for the first"""
+    tot = 0.0
+    for t in range(1, steps + 1):
+        tot += (1 - beta1) / (1 - beta1 ** t) / ((1 - beta2) / (1 - beta2 ** t)) ** 0.5 * sum(beta1 ** (2 * j) / beta2 ** j for j in range(t)) ** 0.5
+    return 2.0 * tot
+
+
+def test_two_chained_steps_with_stride2_phases_match_oracle_elementwise(L, det):
+    """Deterministic mode, two chained (dis_update, gen_update, update_learning_rate) iterations at the reference configuration's shape,
+    256x256 B=3 at full width, with the 4x4 stride-2 Winograd phases on (tuning wino_s2k4 = 1) and off (0), both against ONE fp32 oracle chain.
+    Deterministic mode keeps the stride-2 input gradient on the direct kernels (conv_s2k4_wino_ok); what this adds is the stride-2 FORWARD at
+    a cost-model-chosen shape across chained updates: the per-update filter-transform cache (reset after each update while the weights change
+    in place), the epilogue statistics feeding InstanceNorm, and Adam acting on the result.  B = 3 is the smallest batch whose cost model picks
+    the forward phases in this mode: the executed-FLOP dry run (aclgan_step_executed_flops) is lower with the path on, for both updates.
+    Asserted per network: (i) no element off by more than Adam's own elementwise bound (adam_elementwise_bound: 4.11 lr after two steps),
+    both runs; (ii) the path-on run is not systematically worse than the
+    path-off run (the rule and bounds of CHAIN_BOUNDS); (iii) the path-on run is bit-reproducible."""
+    steps = 2
+    cfg = O.default_config()
+    hard = adam_elementwise_bound(cfg["beta1"], cfg["beta2"], steps) + 0.05       # (+ the slack the three-step test above allows)
+    prev = C.c_int()
+    L.check(L.lib.aclgan_tuning(b"wino_s2k4", 1, C.byref(prev)), "tuning")
+    try:
+        reports = {}
+        for s2 in (1, 0):
+            L.check(L.lib.aclgan_tuning(b"wino_s2k4", s2, None), "tuning")
+            for seed in S2_CHAIN_SEEDS:
+                report, tr, run = chained_report(seed, steps=steps, B=3, S=256, full_width=True)
+                reports[(s2, seed)] = report
+                print("wino_s2k4=%d seed %d: 2 chained deterministic steps @256x256 B=3 vs the fp32 oracle, per network: (max |dp| / lr, share "
+                      "within 0.05 lr, relative L2 of the update)" % (s2, seed), {n: ("%.2f" % a, "%.4f" % b, "%.2e" % c) for n, (a, b, c) in report.items()})
+                for n, (a, b, c) in report.items():
+                    assert a <= hard, (s2, seed, n, a, hard)       # (i)
+                if s2 == 1 and seed == S2_CHAIN_SEEDS[0]:
+                    flops = {}
+                    for which, name in ((0, "gen"), (1, "dis")):
+                        for s in (1, 0):
+                            v = C.c_double()
+                            L.check(L.lib.aclgan_tuning(b"wino_s2k4", s, None), "tuning")
+                            L.check(L.lib.aclgan_step_executed_flops(tr._ctx, which, 3, 256, 256, C.byref(v)), "step_executed_flops")
+                            flops[(name, s)] = v.value
+                        print("deterministic %s_update @256x256 B=3 executed matrix FLOPs, stride-2 phases on / off: %.4e / %.4e"
+                              % (name, flops[(name, 1)], flops[(name, 0)]))
+                        assert flops[(name, 1)] < flops[(name, 0)], (name, flops)
+                    L.check(L.lib.aclgan_tuning(b"wino_s2k4", 1, None), "tuning")
+                    tr2 = run()       # (iii)
+                    assert torch.equal(tr._param[0], tr2._param[0]) and torch.equal(tr._param[1], tr2._param[1])
+                    del tr2
+                del tr, run
+        for seed in S2_CHAIN_SEEDS:
+            for n in reports[(1, seed)]:
+                share_on, share_off = reports[(1, seed)][n][1], reports[(0, seed)][n][1]
+                err_on, err_off = reports[(1, seed)][n][2], reports[(0, seed)][n][2]
+                assert share_on >= share_off - CHAIN_BOUNDS["share_gap"], (seed, n, share_off, share_on)       # (ii)
+                assert err_on <= max(CHAIN_BOUNDS["err_ratio"] * err_off, CHAIN_BOUNDS["err_floor"]), (seed, n, err_off, err_on)
+    finally:
+        L.check(L.lib.aclgan_tuning(b"wino_s2k4", prev.value, None), "tuning")

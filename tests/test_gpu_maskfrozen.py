@@ -8,7 +8,10 @@ Conv2dBlock it back-propagates through, plus the step's two other sign decisions
 the identity losses), the oracle's autograd replays the same update with THOSE masks in place of its own (oracle.act_masks), and what is left is the error of the backward kernels themselves (summation order, Winograd transforms, atomics):
 
     fp32   every gradient tensor <= 1e-3 relative L2 -- measured 1.3e-5 (gen_update) / 2.5e-6 (dis_update) at 256x256 B=2, against 7.2e-3 /
-           4.3e-4 un-frozen in the same run: 398 of 2.5e8 mask elements and ONE of 1.2e6 loss signs differed
+           4.3e-4 un-frozen in the same run: 398 of 2.5e8 mask elements and ONE of 1.2e6 loss signs differed; at the benchmarked B=8 (the
+           stride-2 parity phases at the benchmark's own grids) 1.56e-5 (gen_update, p99 1.56e-5, mean 6.6e-6) / 2.4e-6 (dis_update) against
+           7.6e-3 / 5.5e-4 un-frozen.  A stride-2 input-gradient phase that drops its last 16 channels of K moves the first-layer gradients
+           behind it (enc_content / enc_style model.0, the discriminators' cnns.0.0) to 0.4 - 0.5, at B=2 and at B=8 alike
     bf16 / fp16 against the EMULATED 16-bit contract (oracle.compute_dtype) with the masks frozen: per network bounds below.
 
 Blocks are matched between the two implementations by CONTENT, not by order (the engine builds the passes of an update in its lane order
@@ -49,8 +52,9 @@ def _inputs(B, S, seed):
     return x_a, x_b, z
 
 
-def _hip_update_with_masks(tr, which, x_a, x_b, cfg, z, B, cap_bytes):
-    """run one update with the mask recording on; returns the masks as NCHW bool CPU tensors in batch-sized chunks"""
+def _hip_update_with_masks(tr, which, x_a, x_b, cfg, z, B, cap_bytes, used=None):
+    """run one update with the mask recording on; returns the masks as NCHW bool CPU tensors in batch-sized chunks.
+    used: a one-element list -- only measure the bytes the recording took (end of the last mask), nothing is copied back"""
     from aclgan_amd import _lib as L
     buf = torch.zeros(cap_bytes, dtype=torch.uint8, device="cuda")
     L.check(L.lib.aclgan_debug_capture_masks(tr._ctx, L.ptr(buf), cap_bytes), "debug_capture_masks")
@@ -62,6 +66,9 @@ def _hip_update_with_masks(tr, which, x_a, x_b, cfg, z, B, cap_bytes):
         for i in range(L.lib.aclgan_debug_mask_count(tr._ctx)):
             L.check(L.lib.aclgan_debug_mask_info(tr._ctx, i, dims, C.byref(off), C.byref(act)), "debug_mask_info")
             b, h, w, c = list(dims)
+            if used is not None:
+                used[0] = max(used[0], off.value + b * h * w * c)
+                continue
             m = buf[off.value: off.value + b * h * w * c].view(b, h, w, c).permute(0, 3, 1, 2).bool().cpu()
             if act.value == 100:        # sign of a focus mask's (m - 0.5): channel 3 of the decoder output (2 m - 1)
                 signs.append(m[:, 3:4].contiguous())
@@ -110,19 +117,19 @@ def _grad_errors(tr, orc, nets_, scale=1.0, floor=1e-3):
     return out
 
 
-def _frozen_and_free(T, dt, B, S, seed, forced=False):
+def _frozen_and_free(T, dt, B, S, seed, forced=False, cap_bytes=None):
     """forced: every eligible convolution through the one-launch Winograd kernel (tuning wino_fused = 2): at B = 2 the cost models keep the
     4x4 stride-2 layers and the small grids on the direct kernels / the pipeline, so the default run does not reach those kernels"""
     from aclgan_amd import _lib as L
     old = L.lib.aclgan_set_tuning(b"wino_fused", 2) if forced else None
     try:
-        return _frozen_and_free_impl(T, dt, B, S, seed)
+        return _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes)
     finally:
         if forced:
             L.lib.aclgan_set_tuning(b"wino_fused", old)
 
 
-def _frozen_and_free_impl(T, dt, B, S, seed):
+def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None):
     cfg = O.default_config()
     cfg["display_size"] = 1
     cfg["focus_epsilon"] = 0.5      # smooth fixture (tests/golden/make_golden.py: the default 0.01 has a sign discontinuity of 1e4 at m = 0.5)
@@ -143,7 +150,8 @@ def _frozen_and_free_impl(T, dt, B, S, seed):
         tr = _make(T, cfg, nets, dt)
         if dt:
             assert tr.grad_scale() == scale
-        chunks, signs = _hip_update_with_masks(tr, which, x_a, x_b, cfg, zz, B, 2 << 30 if S >= 256 else 1 << 29)
+        cap = cap_bytes[which] if cap_bytes else (2 << 30 if S >= 256 else 1 << 29)
+        chunks, signs = _hip_update_with_masks(tr, which, x_a, x_b, cfg, zz, B, cap)
         assert chunks, "nothing recorded"
         assert len(signs) == (5 if which == "gen" else 0), len(signs)      # focus B, A, A2 + identity A, B: the oracle's call order (gen_losses)
         with ctx(), O.act_masks() as rec:                    # the oracle with its OWN masks
@@ -162,6 +170,8 @@ def _frozen_and_free_impl(T, dt, B, S, seed):
         print("   unmatched oracle activations (no gradient passes through them in the HIP update):", unmatched[:8], "..." if len(unmatched) > 8 else "")
         print("   worst gradient tensors, masks FROZEN:", [("%.2e" % e, n, k) for e, n, k in e_frozen[:4]])
         print("   worst gradient tensors, masks free  :", [("%.2e" % e, n, k) for e, n, k in e_free[:4]])
+        ef = torch.tensor([e for e, _, _ in e_frozen], dtype=torch.float64)
+        print("   masks FROZEN over all %d gradient tensors: p99 %.2e, mean %.2e" % (len(ef), torch.quantile(ef, 0.99).item(), ef.mean().item()))
         res[which] = dict(frozen=e_frozen, free=e_free, matched=len(replay), acts=len(rec.recorded), unmatched=unmatched)
     return res
 
@@ -187,6 +197,132 @@ def test_backward_parity_with_frozen_masks_fp32(T, forced):
         assert r["matched"] >= (0.3 if which == "dis" else 0.9) * r["acts"], (which, r["matched"], r["acts"], r["unmatched"][:6])
         assert r["frozen"][0][0] <= 1e-3, (which, r["frozen"][:6])       # (measured 1.3e-5 / 2.5e-6: the bound of the review; 1e-4 would hold)
         assert r["free"][0][0] <= 1e-2, (which, r["free"][:6])
+
+
+def _executed_flops(tr, which, B, S, s2k4):
+    """aclgan_step_executed_flops (a dry run of the launchers' own path predicates) with the stride-2 Winograd phases on / off"""
+    from aclgan_amd import _lib as L
+    prev, v = C.c_int(), C.c_double()
+    L.check(L.lib.aclgan_tuning(b"wino_s2k4", s2k4, C.byref(prev)), "tuning")
+    try:
+        L.check(L.lib.aclgan_step_executed_flops(tr._ctx, 0 if which == "gen" else 1, B, S, S, C.byref(v)), "step_executed_flops")
+    finally:
+        L.check(L.lib.aclgan_tuning(b"wino_s2k4", prev.value, None), "tuning")
+    return v.value
+
+
+def _stride2_reached(T, cases):
+    """{(which, B): (FLOPs with the stride-2 phases, without)} at 256x256 on the full-width network, default lanes and paths"""
+    cfg = O.default_config()
+    cfg["display_size"] = 1
+    tr = T.aclgan_Trainer(cfg)
+    out = {}
+    for which, B in cases:
+        out[(which, B)] = (_executed_flops(tr, which, B, 256, 1), _executed_flops(tr, which, B, 256, 0))
+        print("%s_update @256x256 B=%d executed matrix FLOPs, stride-2 phases on / off: %.4e / %.4e" % ((which, B) + out[(which, B)]))
+    return out
+
+
+def test_frozen_mask_cases_reach_the_stride2_phases(T):
+    """the 4x4 stride-2 layers' parity phases (wino_fused_s2k4_ok's cost model): at the benchmarked B = 8 both updates take them (forward and
+    input gradient of CE1/CE2/SE1/SE2, the discriminators' layers 1-2, the input gradient of SE3); at B = 2 the generator update already
+    takes the input-gradient phases of CE1 / SE1, which the default-paths case above runs.  Path on = fewer executed FLOPs."""
+    fl = _stride2_reached(T, (("dis", 8), ("gen", 8), ("gen", 2)))
+    for key, (on, off) in fl.items():
+        assert on < off, (key, on, off)
+
+
+def _mask_capture_bytes(T, B, S, seed):
+    """mask-recording buffer for an update at batch B: the bytes the same update takes at B = 2 (aclgan_debug_mask_info's offsets; every
+    recorded mask is a multiple of the batch), scaled by B / 2, plus 10 % and 64 MB of margin"""
+    cfg = O.default_config()
+    cfg["display_size"] = 1
+    cfg["focus_epsilon"] = 0.5
+    nets = O.test_nets(cfg, 0)
+    x_a, x_b, z = _inputs(2, S, seed)
+    out = {}
+    for which, zz in (("dis", z[:3]), ("gen", z[3:])):
+        used = [0]
+        _hip_update_with_masks(_make(T, cfg, nets), which, x_a, x_b, cfg, zz, 2, 2 << 30, used=used)
+        assert used[0] > 0
+        out[which] = int(used[0] * B / 2 * 1.1) + (64 << 20)
+    return out
+
+
+def test_backward_parity_with_frozen_masks_fp32_benchmarked_batch(T):
+    """256x256 B=8, fp32, default paths and lanes: the benchmarked schedule.  The B = 2 cases above leave most of the stride-2 parity phases
+    to the cost model's direct kernels; here they run at the grids and splits the benchmark uses (test_frozen_mask_cases_reach_the_stride2_phases).
+    With the HIP update's own masks replayed by the oracle every gradient tensor agrees to 1e-3 relative L2, the bound of the B = 2 cases;
+    the masks-free figure is printed beside it (tests/test_gpu_fullsize.py holds that one to 1e-2)."""
+    cap = _mask_capture_bytes(T, 8, 256, 33)
+    res = _frozen_and_free(T, None, 8, 256, 33, cap_bytes=cap)
+    for which in ("dis", "gen"):
+        r = res[which]
+        assert r["matched"] >= (0.3 if which == "dis" else 0.9) * r["acts"], (which, r["matched"], r["acts"], r["unmatched"][:6])
+        assert r["frozen"][0][0] <= 1e-3, (which, r["frozen"][:6])
+
+
+def _sample_oracle(nets, cfg, x_a, z1, z2, z3):
+    """sample()'s nine outputs (trainer.py:179-245, focus branch) from the fp32 oracle"""
+    gc = cfg["gen"]
+    AB, BA = nets["gen_AB"], nets["gen_BA"]
+    want = [[] for _ in range(9)]
+    with torch.no_grad():
+        for i in range(x_a.size(0)):
+            xa = x_a[i:i + 1]
+            c1, s1 = O.content_encode(BA, xa, gc), O.style_encode(BA, xa, gc)
+            o = O.decode(BA, c1, z1[i:i + 1], gc); a_fake = O.focus_translation(o[:, :3], xa, o[:, 3:]); m_a = o[:, 3:]
+            o = O.decode(BA, c1, s1, gc); a_rec, m_rec = o[:, :3], o[:, 3:]
+            o = O.decode(AB, O.content_encode(AB, xa, gc), z2[i:i + 1], gc); b_fake = O.focus_translation(o[:, :3], xa, o[:, 3:]); m_b = o[:, 3:]
+            o = O.decode(BA, O.content_encode(BA, b_fake, gc), z3[i:i + 1], gc); a2 = O.focus_translation(o[:, :3], b_fake, o[:, 3:])
+            for lst, t in zip(want, (xa, a_fake, m_a, b_fake, m_b, a2, o[:, 3:], a_rec, m_rec)):
+                lst.append(t)
+    return [torch.cat(w) for w in want]
+
+
+def test_forward_arena_follows_tuning_changes(T):
+    """sample() at 256x256 B=2 (full width), then tuning wino_fused = 2 and sample() again.  sample() runs per image, so its forward-only
+    arena is sized for B = 1; mode 2 sends every eligible 4x4 stride-2 layer to the parity phases, whose filter-transform scratch grows that
+    arena (measured by the dry run: 357.6 -> 431.0 MB).  A forward-only arena is valid for one tuning epoch, like a training arena: the
+    second call must size and bind again, and both calls must match the oracle at the bound of tests/test_gpu_step.py's sample test."""
+    from aclgan_amd import _lib as L
+    cfg = O.default_config()
+    cfg["display_size"] = 2
+    nets = O.test_nets(cfg, 0)
+    tr = _make(T, cfg, nets)
+    g = torch.Generator().manual_seed(37)
+    x_a = torch.rand(2, 3, 256, 256, generator=g) * 2 - 1
+    x_b = torch.rand(2, 3, 256, 256, generator=g) * 2 - 1
+
+    def fwd_bytes():
+        v = C.c_size_t()
+        L.check(L.lib.aclgan_forward_workspace_bytes(tr._ctx, 1, 256, 256, C.byref(v)), "forward_workspace_bytes")
+        return v.value
+
+    def rel(a, b):
+        a = a.detach().double().cpu(); b = b.detach().double().cpu()
+        return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+
+    want = None
+    prev = C.c_int()
+    before = fwd_bytes()
+    outs = [tr.sample(x_a, x_b)]
+    assert tr._ws_shape[3] is False and tr._ws.numel() >= before
+    L.check(L.lib.aclgan_tuning(b"wino_fused", 2, C.byref(prev)), "tuning")
+    try:
+        after = fwd_bytes()
+        print("forward-only workspace @256x256 B=1: %d bytes, %d with wino_fused = 2" % (before, after))
+        assert after > before, (before, after)
+        outs.append(tr.sample(x_a, x_b))
+        torch.cuda.synchronize()
+        assert tr._ws.numel() >= after
+    finally:
+        L.check(L.lib.aclgan_tuning(b"wino_fused", prev.value, None), "tuning")
+    want = _sample_oracle(nets, cfg, x_a, tr.z_1.cpu(), tr.z_2.cpu(), tr.z_3.cpu())
+    for run, out in enumerate(outs):
+        errs = [rel(got, w) for got, w in zip(out, want)]
+        print("sample() run %d max-abs rel errors vs the oracle:" % run, ["%.2e" % e for e in errs])
+        assert max(errs) < 1e-3, (run, errs)
 
 
 # 16-bit: bounds per network group <= 2x the measured value, masks and signs frozen, against the emulated contract.  Measured (round 6,

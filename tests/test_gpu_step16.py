@@ -69,6 +69,22 @@ def _rel(a, b):
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
 
 
+def _dist(a, b):
+    """(p99, mean) of |a - b| / max |b|: the distribution beside _rel's maximum -- a subtly wrong 16-bit kernel shifts the bulk of the
+    elements, which one outlier pixel's max-abs bound cannot show"""
+    a = a.detach().double().cpu(); b = b.detach().double().cpu()
+    e = ((a - b).abs() / b.abs().max().clamp_min(1e-30)).flatten()
+    return torch.quantile(e.float(), 0.99).item(), e.mean().item()
+
+
+# x_A2_fake against the fp32 oracle: (p99, mean) of |got - ref| / max |ref|, bounds = 2x the value measured on the MI355X.  Keys: (dtype, image
+# size) for test_forward_and_losses_16bit (B = 2), (dtype, batch) for test_16bit_at_its_per_gpu_batch (256x256).  Measured:
+#   bf16  64x64 2.28e-2 / 5.58e-3,  256x256 2.42e-2 / 6.50e-3,  B=8  2.73e-2 / 7.28e-3
+#   fp16  64x64 2.81e-3 / 7.00e-4,  256x256 3.06e-3 / 8.21e-4,  B=32 2.59e-3 / 6.94e-4
+X2_DIST = {("bf16", 64): (4.6e-2, 1.12e-2), ("bf16", 256): (4.9e-2, 1.3e-2), ("bf16", 8): (5.5e-2, 1.5e-2),
+           ("fp16", 64): (5.7e-3, 1.4e-3), ("fp16", 256): (6.2e-3, 1.65e-3), ("fp16", 32): (5.2e-3, 1.4e-3)}
+
+
 def _inputs(B, S, seed):
     g = torch.Generator().manual_seed(seed)
     x_a = torch.rand(B, 3, S, S, generator=g) * 2 - 1
@@ -119,6 +135,9 @@ def test_forward_and_losses_16bit(T, dt, B, S):
     # (rounds 5-6) -> 6.0e-2 when the LayerNorm partials started to be combined in 64 slices (round 6), 4.7e-2 against the emulated contract.
     bad = {k: v for k, v in worst.items() if not v < (max(FTOL[dt], ETOL_F[dt]) if k == "x_A2_fake" else FTOL[dt])}
     assert not bad, bad
+    p99, mean = _dist(xA2, fw["x_A2_fake"])
+    print("%s x_A2_fake @%dx%d B=%d vs the fp32 oracle: p99 %.3e, mean %.3e (relative absolute error)" % (dt, S, S, B, p99, mean))
+    assert p99 <= X2_DIST[(dt, S)][0] and mean <= X2_DIST[(dt, S)][1], (p99, mean, X2_DIST[(dt, S)])
     bad = {k: v for k, v in worst_e.items() if not v < ETOL_F[dt]}
     assert not bad, ("emulated", bad)
     assert worst_e["s_2"] < ETOL_S2[dt], ("emulated s_2", worst_e["s_2"])
@@ -284,6 +303,9 @@ def test_16bit_at_its_per_gpu_batch(T, dt, B, NS):
     # bf16 B=8 (round 5), every other tensor <= 3.9e-2; it gets the bound the docstring above states for it against the emulated contract
     bad = {k: v for k, v in worst.items() if not v < (max(FTOL[dt], ETOL_F[dt]) if k == "x_A2_fake" else FTOL[dt])}
     assert not bad, bad
+    p99, mean = _dist(xA2[:NS], fw["x_A2_fake"])
+    print("%s B=%d x_A2_fake vs the fp32 oracle on samples 0..%d: p99 %.3e, mean %.3e (relative absolute error)" % (dt, B, NS - 1, p99, mean))
+    assert p99 <= X2_DIST[(dt, B)][0] and mean <= X2_DIST[(dt, B)][1], (p99, mean, X2_DIST[(dt, B)])
     # ---- the update at B=32 ----
     gen0 = tr._param[0].clone(); dis0 = tr._param[1].clone()
     assert tr.grad_scale() == SCALE[dt]
