@@ -306,24 +306,33 @@ _QDT = None   # torch.bfloat16 / torch.float16 while emulating, else None (= the
 _QSCALE = 1.0  # fp16 loss scale S: every gradient that enters a 16-bit GEMM is S*dy (the build seeds the backward with S)
 _QSTORE = True  # emulate the 16-bit storage as well (compute_dtype(..., storage=False): the round-2 contract, fp32 storage)
 _QCO16 = True   # ... including the conv outputs in front of normalisation layers (the build's ACLGAN_CO16 switch)
+_QUP5D = "merged"  # input gradient of the sub-pixel layers: "merged" (the default plan) or "plain" (the deterministic plan, see compute_dtype)
 
 
 class compute_dtype:
     """with compute_dtype("bf16"): ... / with compute_dtype("fp16", loss_scale=65536.0): ...
-    conv_block emulates the 16-bit MFMA contract inside the block (gradients come out UNscaled)."""
+    conv_block emulates the 16-bit MFMA contract inside the block (gradients come out UNscaled).
 
-    def __init__(self, name, loss_scale=1.0, storage=True):
+    up5_dgrad: the 16-bit input gradient of the sub-pixel ("Upsample(2) + 5x5") layers.  "merged" (default): interior pixels through the
+    rounded merged 3x3 phase filters, the ring through the rounded 5x5 -- the default plan (conv_fast16.hip dgrad16_t).  "plain": the rounded
+    5x5 on the upsampled grid everywhere -- the deterministic plan, which runs these layers as the plain upsample + 5x5 convolution.  Forward
+    and weight gradient are the same in both plans."""
+
+    def __init__(self, name, loss_scale=1.0, storage=True, up5_dgrad="merged"):
+        if up5_dgrad not in ("merged", "plain"):
+            raise ValueError("up5_dgrad must be 'merged' or 'plain', not %r" % (up5_dgrad,))
         self.dt = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}[name]
         self.scale = float(loss_scale)
         self.storage = bool(storage)
+        self.up5_dgrad = up5_dgrad
 
     def __enter__(self):
-        global _QDT, _QSCALE, _QSTORE
-        self.prev, _QDT, _QSCALE, _QSTORE = (_QDT, _QSCALE, _QSTORE), self.dt, self.scale, self.storage
+        global _QDT, _QSCALE, _QSTORE, _QUP5D
+        self.prev, _QDT, _QSCALE, _QSTORE, _QUP5D = (_QDT, _QSCALE, _QSTORE, _QUP5D), self.dt, self.scale, self.storage, self.up5_dgrad
 
     def __exit__(self, *a):
-        global _QDT, _QSCALE, _QSTORE
-        _QDT, _QSCALE, _QSTORE = self.prev
+        global _QDT, _QSCALE, _QSTORE, _QUP5D
+        _QDT, _QSCALE, _QSTORE, _QUP5D = self.prev
 
 
 def _q(t):
@@ -403,7 +412,7 @@ class _ConvQ(torch.autograd.Function):
         with torch.enable_grad():
             # ---- dgrad ----
             xv = x.detach().requires_grad_(True)
-            if d16 and ctx.up5:
+            if d16 and ctx.up5 and _QUP5D == "merged":
                 dyq = _qg(dy)
                 H, W = x.shape[2], x.shape[3]
                 ring = torch.ones_like(dyq)

@@ -3,7 +3,8 @@
 (scripts/trace_step.sh), B = a kernel trace of the operator tests.  The launch key is scripts/rocpd_bygrid.py's (imported from it).
 
 usage: python scripts/launch_coverage.py A1.db[,A2.db ...] B1.db[,B2.db ...] [regex of kernel names]
-       default regex: the convolution, Winograd, normalisation and split-K / weight-gradient finish kernels"""
+       default regex: the convolution (fold gathers included), Winograd, normalisation and split-K / weight-gradient finish kernels, and the
+       reductions whose plan depends on the deterministic mode: ordered column sums, ordered slice sums, the O-sliced linear input gradient"""
 import os
 import re
 import sys
@@ -11,7 +12,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from rocpd_bygrid import launches  # noqa: E402
 
-DEFAULT = r"conv_|wino_|norm_|fwd_split_finish|wgrad_.*finish|colsum"
+DEFAULT = r"conv_|wino_|norm_|fwd_split_finish|wgrad_.*finish|colsum|reduce_slices|linear_dx"
 
 
 def counts(paths):

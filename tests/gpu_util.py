@@ -1,5 +1,6 @@
 """helpers for the -m gpu tests: layout conversion and thin wrappers over the C ABI."""
 import ctypes as C
+from contextlib import contextmanager
 
 import torch
 
@@ -24,6 +25,19 @@ def rel_err(a, b):
     a = a.detach().double().cpu()
     b = b.detach().double().cpu()
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+
+
+@contextmanager
+def deterministic_mode(L, on):
+    """the library's process-wide deterministic switch set to `on` for the body and restored to its previous value afterwards (1 when the
+    whole suite runs under ACLGAN_DETERMINISTIC=1); on = False sets mode 0 explicitly"""
+    prev = L.lib.aclgan_get_deterministic()
+    L.check(L.lib.aclgan_set_deterministic(1 if on else 0))
+    assert L.lib.aclgan_get_deterministic() == (1 if on else 0)
+    try:
+        yield
+    finally:
+        L.check(L.lib.aclgan_set_deterministic(prev))
 
 
 def conv_desc(L, B, Hi, Wi, Ci, Co, k, s, p, up=0, act="none"):

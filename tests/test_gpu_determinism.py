@@ -34,11 +34,9 @@ def L():
 @pytest.fixture()
 def det(L):
     """deterministic mode for one test; the process-wide switch is restored afterwards"""
-    prev = L.lib.aclgan_get_deterministic()      # (1 when the whole suite runs under ACLGAN_DETERMINISTIC=1)
-    L.check(L.lib.aclgan_set_deterministic(1))
-    assert L.lib.aclgan_get_deterministic() == 1
-    yield
-    L.check(L.lib.aclgan_set_deterministic(prev))
+    from gpu_util import deterministic_mode
+    with deterministic_mode(L, True):
+        yield
 
 
 # (B, Hi, Wi, Ci, Co, k, s, p, up): one per default-mode atomics site

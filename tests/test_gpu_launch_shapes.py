@@ -23,8 +23,17 @@ row, slice or tile seam.  This module closes that gap:
   * the small operators (linear, MLP, global average pool, avgpool, losses) at the step's batch sizes and pixel counts.
 
 Per-sample passes (forward, input gradient) are checked on samples 0, B // 2 and B - 1 while the kernel runs the whole batch; the weight
-gradient sums over the batch, so its reference is the whole batch.  A failure names the workload, the layer (its parameter names), the pass
-and the worst element with its position.  Run with -s for the table of worst errors."""
+gradient sums over the batch, so its reference is the whole batch.  A failure names the workload, the mode, the layer (its parameter names),
+the pass and the worst element with its position.  Run with -s for the table of worst errors.
+
+Both plans of the library are checked (the `mode` parameter, ids "<workload>" and "<workload>-det"; the mode is set explicitly either way, so
+the module means the same under ACLGAN_DETERMINISTIC=1).  The deterministic plan (aclgan_set_deterministic) replaces every fp32 atomic of the
+default plan: padded-grid input gradients with an ordered fold, the Winograd ring stored on a zeroed grid, per-slice weight-gradient copies
+added in order, ordered bias column sums, no split-K.  In that mode every scratch buffer is sized after the mode is set and filled with NaN
+before the call, so a padded-grid position no launch writes (or a memset misses) shows in the output instead of a zero the allocator happened
+to return; every backward pass runs a second time on scratch filled with +inf and must give the same bits.  Its one contract difference: the
+16-bit input gradient of the sub-pixel layers is the plain rounded 5x5 (oracle compute_dtype(up5_dgrad="plain")), not the merged phase
+filters of the default plan."""
 import ctypes as C
 import os
 import time
@@ -53,7 +62,8 @@ WORKLOADS = [
 ]
 WL = {w[0]: w for w in WORKLOADS}
 
-RESULTS = []          # (workload, layer, pass, worst error, bound)
+RESULTS = []          # (workload/mode, layer, pass, worst error, bound)
+MODES = ("default", "det")
 
 
 @pytest.fixture(scope="module")
@@ -68,6 +78,23 @@ def L():
         print("workload | layer | pass | worst | bound")
         for wl, lay, ps, err, bound in RESULTS:
             print("%s | %s | %s | %.2e | %.1e" % (wl, lay, ps, err, bound))
+
+
+@pytest.fixture
+def mode(L, request):
+    """the library's plan for one test: "default" (mode 0, set explicitly) or "det"; the previous mode is restored afterwards"""
+    from gpu_util import deterministic_mode
+    with deterministic_mode(L, request.param == "det"):
+        yield request.param
+
+
+def _modes(values):
+    """(value, mode) parameters: the default plan keeps the value's own id, the deterministic plan's id ends in -det"""
+    return [pytest.param(v, m, id=str(v) if m == "default" else "%s-det" % v) for m in MODES for v in values]
+
+
+def _det(L):
+    return L.lib.aclgan_get_deterministic() == 1
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -196,8 +223,13 @@ def _samples(B):
     return sorted({0, B // 2, B - 1})
 
 
-def _scr(nbytes):
-    return torch.empty(int(nbytes) // 4 + 64, device="cuda")
+def _scr(nbytes, fill=None):
+    """scratch of nbytes (+ 256 bytes); fill: the value every element starts as (deterministic mode: NaN, +inf for a second run)"""
+    n = int(nbytes) // 4 + 64
+    return torch.empty(n, device="cuda") if fill is None else torch.full((n,), fill, device="cuda")
+
+
+NAN, INF = float("nan"), float("inf")
 
 
 def _where(idx, shape, what, rows=None):
@@ -229,8 +261,8 @@ def _where(idx, shape, what, rows=None):
 class Check:
     """collects the comparisons of one test; fails at the end with every offending (layer, pass)"""
 
-    def __init__(self, wl):
-        self.wl, self.bad = wl, []
+    def __init__(self, wl, mode=None):
+        self.wl, self.bad = wl if mode is None else "%s/%s" % (wl, mode), []
 
     def __call__(self, lay, ps, got, ref, bound, what="act", rows=None):
         got = got.detach().double()
@@ -369,7 +401,7 @@ def check_norm_layer(L, chk, lay, g, xc, st, dt_code, gen, stats=None, chunk=0):
     bptr = None if P is None else C.c_void_p(P.data_ptr() + 4 * (bcol if kind == "adain" else Co))
     res = (torch.randn(B, Ho, Wo, Co, device="cuda", generator=gen)).to(T(st[2])) if use_res else None
     nst = B if kind == "ln" else B * Co
-    scr = _scr(L.lib.aclgan_norm_scratch_bytes(B, HW, Co))
+    scr = _scr(L.lib.aclgan_norm_scratch_bytes(B, HW, Co), NAN if _det(L) else None)
     stf = (C.c_int * 3)(st[0], st[1], st[2])
 
     def fwd(stats_, chunk_, ss_):
@@ -477,11 +509,13 @@ def check_fp32_layer(L, chk, g, ent, seed, passes=("fwd", "dgrad", "wgrad"), nor
     x, w, b, gen = _tensors(g, seed)
     S = _samples(B)
     w64, b64 = _oihw64(w), b.double()
+    det = _det(L)
+    fill = NAN if det else None
     if "fwd" in passes:
         d = _desc(L, g, act if norm == "none" else "none")
         if norm == "none":
             y = torch.full((B, Ho, Wo, Co), float("nan"), device="cuda")
-            L.check(L.lib.aclgan_conv2d_fwd_ws(C.byref(d), L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y), L.ptr(_scr(L.lib.aclgan_conv2d_fwd_scratch_bytes(C.byref(d)))),
+            L.check(L.lib.aclgan_conv2d_fwd_ws(C.byref(d), L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y), L.ptr(_scr(L.lib.aclgan_conv2d_fwd_scratch_bytes(C.byref(d)), fill)),
                                                L.stream_ptr()), "conv2d_fwd_ws")
             ref = _ref_conv(_nchw64(x[S]), w64, b64, g, act).permute(0, 2, 3, 1)
             chk(lay, "fwd", y[S], ref, TOL, rows=S)
@@ -497,7 +531,7 @@ def check_fp32_layer(L, chk, g, ent, seed, passes=("fwd", "dgrad", "wgrad"), nor
             fused = C.c_int(-1)
             L.check(L.lib.aclgan_conv2d_block_fwd(C.byref(d), L.NORM[norm], L.ACT[act], L.ptr(x), L.ptr(w), L.ptr(b), nwp, nbp, wstride, L.ptr(res),
                                                   L.ptr(yc), L.ptr(y), L.ptr(mean), L.ptr(rstd),
-                                                  L.ptr(_scr(L.lib.aclgan_conv2d_block_fwd_scratch_bytes(C.byref(d)))), C.byref(fused), L.stream_ptr()),
+                                                  L.ptr(_scr(L.lib.aclgan_conv2d_block_fwd_scratch_bytes(C.byref(d)), fill)), C.byref(fused), L.stream_ptr()),
                     "conv2d_block_fwd")
             ycr = _ref_conv(_nchw64(x[S]), w64, b64, g)
             chk(lay, "fwd conv", yc[S], ycr.permute(0, 2, 3, 1), TOL, rows=S)
@@ -514,33 +548,48 @@ def check_fp32_layer(L, chk, g, ent, seed, passes=("fwd", "dgrad", "wgrad"), nor
     if "dgrad" in passes or "wgrad" in passes:
         dy = torch.randn(B, Ho, Wo, Co, device="cuda", generator=gen)
     if "dgrad" in passes:
-        scr = _scr(L.lib.aclgan_conv2d_dgrad_scratch_bytes(C.byref(d)))
-        dx = torch.full((B, Hi, Wi, Ci), float("nan"), device="cuda")
-        L.check(L.lib.aclgan_conv2d_dgrad(C.byref(d), L.ptr(dy), L.ptr(w), L.ptr(dx), L.ptr(scr), 0, L.stream_ptr()), "conv2d_dgrad")
+        nb = L.lib.aclgan_conv2d_dgrad_scratch_bytes(C.byref(d))
+
+        def dgrad(out, acc, fill_):
+            scr = _scr(nb, fill_)
+            L.check(L.lib.aclgan_conv2d_dgrad(C.byref(d), L.ptr(dy), L.ptr(w), L.ptr(out), L.ptr(scr), acc, L.stream_ptr()), "conv2d_dgrad")
+            return out
+        dx = dgrad(torch.full((B, Hi, Wi, Ci), NAN, device="cuda"), 0, fill)
         ref = _ref_dgrad(dy[S], w64, g, (len(S), Ci, Hi, Wi))
         chk(lay, "dgrad", dx[S], ref, TOL, rows=S)
         # accumulate (a tensor with two consumers, the ResBlock input): onto a nonzero base of the gradient's own magnitude
         base = torch.randn(B, Hi, Wi, Ci, device="cuda", generator=gen) * float(ref.abs().max())
-        acc = base.clone()
-        L.check(L.lib.aclgan_conv2d_dgrad(C.byref(d), L.ptr(dy), L.ptr(w), L.ptr(acc), L.ptr(scr), 1, L.stream_ptr()), "conv2d_dgrad")
+        acc = dgrad(base.clone(), 1, fill)
         chk(lay, "dgrad accumulate", (acc[S].double() - base[S].double()), ref, TOL, rows=S)
+        if det:       # a second run on scratch poisoned differently: the same bits
+            chk.equal(lay, "dgrad det rerun", dgrad(torch.full((B, Hi, Wi, Ci), NAN, device="cuda"), 0, INF), dx)
+            chk.equal(lay, "dgrad accumulate det rerun", dgrad(base.clone(), 1, INF), acc)
     if "wgrad" in passes:
-        dw = torch.zeros(Co, k, k, Ci, device="cuda"); db = torch.zeros(Co, device="cuda")      # (the weight gradient accumulates)
-        L.check(L.lib.aclgan_conv2d_wgrad_ws(C.byref(d), L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(db),
-                                             L.ptr(_scr(L.lib.aclgan_conv2d_wgrad_scratch_bytes(C.byref(d)))), L.stream_ptr()), "conv2d_wgrad_ws")
+        nb = L.lib.aclgan_conv2d_wgrad_scratch_bytes(C.byref(d))
+
+        def wgrad(fill_):
+            dw = torch.zeros(Co, k, k, Ci, device="cuda"); db = torch.zeros(Co, device="cuda")      # (the weight gradient accumulates)
+            L.check(L.lib.aclgan_conv2d_wgrad_ws(C.byref(d), L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(db), L.ptr(_scr(nb, fill_)), L.stream_ptr()),
+                    "conv2d_wgrad_ws")
+            return dw, db
+        dw, db = wgrad(fill)
         rdw, rdb = _ref_wgrad(x, dy, w, g)
         chk(lay, "wgrad dw", dw, rdw, TOL, what="w")
         chk(lay, "wgrad db", db, rdb, TOL, what="")
+        if det:
+            dw2, db2 = wgrad(INF)
+            chk.equal(lay, "wgrad dw det rerun", dw2, dw)
+            chk.equal(lay, "wgrad db det rerun", db2, db)
 
 
-@pytest.mark.parametrize("wl", ["fp32_256_b8", "fp32_512_b4", "fp32_256_b3"])
-def test_fp32_layers_at_launch_shape(L, wl):
+@pytest.mark.parametrize("wl,mode", _modes(["fp32_256_b8", "fp32_512_b4", "fp32_256_b3"]), indirect=["mode"])
+def test_fp32_layers_at_launch_shape(L, wl, mode):
     t0 = time.time()
-    chk = Check(wl)
+    chk = Check(wl, mode)
     for i, (g, ent) in enumerate(launch_table(wl).items()):
         check_fp32_layer(L, chk, g, ent, 100 + i, norm_storage=(0, 0, 0, 0, 0, 0) if g[10] != "none" else None)
     torch.cuda.synchronize()
-    print("\n%s: %d layers in %.1f s" % (wl, len(launch_table(wl)), time.time() - t0))
+    print("\n%s/%s: %d layers in %.1f s" % (wl, mode, len(launch_table(wl)), time.time() - t0))
     chk.done()
 
 
@@ -555,10 +604,11 @@ def _packs(L, w, code):
     return w16, w16t
 
 
-def _ref16(x, w, b, g, dt, dy=None, want=("y",)):
-    """the 16-bit compute contract in float64 (oracle _ConvQ: both operands rounded; the sub-pixel layers round the merged phase filters)"""
+def _ref16(x, w, b, g, dt, dy=None, up5_dgrad="merged"):
+    """the 16-bit compute contract in float64 (oracle _ConvQ: both operands rounded; the sub-pixel layers round the merged phase filters
+    in the forward, and in the input gradient of the default plan -- up5_dgrad="plain": the rounded 5x5, the deterministic plan)"""
     B, Hi, Wi, Ci, Co, k, s, p, up = g[:9]
-    with O.compute_dtype(dt, storage=False):
+    with O.compute_dtype(dt, storage=False, up5_dgrad=up5_dgrad):
         xr = _nchw64(x).requires_grad_(dy is not None)
         wr = _oihw64(w).requires_grad_(dy is not None)
         y = O._ConvQ.apply(xr, wr, b.double(), s, p, bool(up), True, True, True)
@@ -594,6 +644,8 @@ def check_16bit_layer(L, chk, g, ent, dt, seed, last_dec_res):
     x, w, b, gen = _tensors(g, seed + 7, grid_w=bool(up))
     xq = x.to(T).float()                      # the operand values (a 16-bit x is the same numbers)
     S = _samples(B)
+    det = _det(L)
+    fill = NAN if det else None
     w16p, w16t = _packs(L, w, code)
     if f16:
         yref = _ref16(xq[S], w, b, g, dt)
@@ -617,12 +669,12 @@ def check_16bit_layer(L, chk, g, ent, dt, seed, last_dec_res):
                 check_norm_layer(L, chk, lay, g, yc, norm_st, code, gen, stats if chunk else None, chunk)
         y = torch.full((B, Ho, Wo, Co), float("nan"), device="cuda")
         L.check(L.lib.aclgan_conv2d_fwd16_x16(C.byref(d_f), code, L.ptr(x16), L.ptr(w), L.ptr(w16p), L.ptr(b), L.ptr(y),
-                                              L.ptr(_scr(L.lib.aclgan_conv2d_fwd16_scratch_bytes(C.byref(d_f)))), L.stream_ptr()), "conv2d_fwd16_x16")
+                                              L.ptr(_scr(L.lib.aclgan_conv2d_fwd16_scratch_bytes(C.byref(d_f)), fill)), L.stream_ptr()), "conv2d_fwd16_x16")
         chk(lay, "fwd16_x16", y[S], yref, TOL, rows=S)
         if Co % 64 == 0 and norm == "none" and ent["out16"]:      # a 16-bit y (the step's wide layers without a norm, where the LDS-DMA kernel does not run them) == y rounded
             yst = torch.full((B, Ho, Wo, Co), float("nan"), device="cuda").to(T)
             L.check(L.lib.aclgan_conv2d_fwd16_x16_st(C.byref(d_f), code, L.ptr(x16), L.ptr(w), L.ptr(w16p), L.ptr(b), L.ptr(yst), code,
-                                                     L.ptr(_scr(L.lib.aclgan_conv2d_fwd16_scratch_bytes(C.byref(d_f)))), L.stream_ptr()),
+                                                     L.ptr(_scr(L.lib.aclgan_conv2d_fwd16_scratch_bytes(C.byref(d_f)), fill)), L.stream_ptr()),
                     "conv2d_fwd16_x16_st")
             chk.equal(lay, "fwd16_x16 16-bit y == fp32 rounded", yst, y.to(T))
         if norm != "none" and not s_fwd:      # the step's norm reads this conv output (fp32, own statistics pass)
@@ -631,56 +683,79 @@ def check_16bit_layer(L, chk, g, ent, dt, seed, last_dec_res):
         dy = torch.randn(B, Ho, Wo, Co, device="cuda", generator=gen)
         dyq = dy.to(T).float()
     if d16:
-        gx, _ = _ref16(xq[S], w, b, g, dt, dyq[S])
-        dscr = _scr(L.lib.aclgan_conv2d_dgrad16_scratch_bytes(C.byref(d_b)) + 256)
-        dx = torch.full((B, Hi, Wi, Ci), float("nan"), device="cuda")
-        L.check(L.lib.aclgan_conv2d_dgrad16(C.byref(d_b), code, L.ptr(dyq), L.ptr(w), L.ptr(w16t), L.ptr(dx), 0, L.ptr(dscr), L.stream_ptr()), "conv2d_dgrad16")
+        # the deterministic plan runs the sub-pixel layers as the plain upsample + 5x5 (conv_fast16.hip dgrad16_t): its own rounding contract
+        gx, _ = _ref16(xq[S], w, b, g, dt, dyq[S], up5_dgrad="plain" if det else "merged")
+        nb = L.lib.aclgan_conv2d_dgrad16_scratch_bytes(C.byref(d_b))
+        if det:       # one writer per position of the padded gradient grid, then the fold: the scratch holds that whole grid
+            Hp, Wp = (Hi << up) + 2 * p, (Wi << up) + 2 * p
+            assert nb >= 4 * B * Hp * Wp * Ci, (chk.wl, lay, "dgrad16 scratch", nb, 4 * B * Hp * Wp * Ci)
+
+        def dgrad16(out, acc, fill_):
+            L.check(L.lib.aclgan_conv2d_dgrad16(C.byref(d_b), code, L.ptr(dyq), L.ptr(w), L.ptr(w16t), L.ptr(out), acc, L.ptr(_scr(nb + 256, fill_)),
+                                                L.stream_ptr()), "conv2d_dgrad16")
+            return out
+        dx = dgrad16(torch.full((B, Hi, Wi, Ci), NAN, device="cuda"), 0, fill)
         chk(lay, "dgrad16", dx[S], gx, TOL, rows=S)
         base = torch.randn(B, Hi, Wi, Ci, device="cuda", generator=gen) * float(gx.abs().max())
-        acc = base.clone()
-        L.check(L.lib.aclgan_conv2d_dgrad16(C.byref(d_b), code, L.ptr(dyq), L.ptr(w), L.ptr(w16t), L.ptr(acc), 1, L.ptr(dscr), L.stream_ptr()), "conv2d_dgrad16")
+        acc = dgrad16(base.clone(), 1, fill)
         chk(lay, "dgrad16 accumulate", acc[S].double() - base[S].double(), gx, TOL, rows=S)
+        if det:
+            chk.equal(lay, "dgrad16 det rerun", dgrad16(torch.full((B, Hi, Wi, Ci), NAN, device="cuda"), 0, INF), dx)
+            chk.equal(lay, "dgrad16 accumulate det rerun", dgrad16(base.clone(), 1, INF), acc)
         if L.lib.aclgan_conv16s_ok(C.byref(d_b), 1):
             dy16 = dy.to(T)
-            sscr = _scr(L.lib.aclgan_conv2d_dgrad16s_scratch_bytes(C.byref(d_b)))
-            dx32 = torch.full((B, Hi, Wi, Ci), float("nan"), device="cuda")
-            L.check(L.lib.aclgan_conv2d_dgrad16s(C.byref(d_b), code, L.ptr(dy16), L.ptr(w16t), L.ptr(dx32), 0, 0, L.ptr(sscr), L.stream_ptr()), "conv2d_dgrad16s")
+            snb = L.lib.aclgan_conv2d_dgrad16s_scratch_bytes(C.byref(d_b))
+
+            def dgrad16s(out, st_, acc_, fill_):
+                L.check(L.lib.aclgan_conv2d_dgrad16s(C.byref(d_b), code, L.ptr(dy16), L.ptr(w16t), L.ptr(out), st_, acc_, L.ptr(_scr(snb, fill_)),
+                                                     L.stream_ptr()), "conv2d_dgrad16s")
+                return out
+            dx32 = dgrad16s(torch.full((B, Hi, Wi, Ci), NAN, device="cuda"), 0, 0, fill)
             chk(lay, "dgrad16s", dx32[S], gx, 2 * ULP[dt], rows=S)
-            dx16 = torch.full((B, Hi, Wi, Ci), float("nan"), device="cuda").to(T)
-            L.check(L.lib.aclgan_conv2d_dgrad16s(C.byref(d_b), code, L.ptr(dy16), L.ptr(w16t), L.ptr(dx16), code, 0, L.ptr(sscr), L.stream_ptr()), "conv2d_dgrad16s")
+            dx16 = dgrad16s(torch.full((B, Hi, Wi, Ci), NAN, device="cuda").to(T), code, 0, fill)
             chk.equal(lay, "dgrad16s 16-bit dx == fp32 rounded", dx16, dx32.to(T))
             b16 = base.to(T)
-            acc16 = b16.clone()
-            L.check(L.lib.aclgan_conv2d_dgrad16s(C.byref(d_b), code, L.ptr(dy16), L.ptr(w16t), L.ptr(acc16), code, 1, L.ptr(sscr), L.stream_ptr()), "conv2d_dgrad16s")
+            acc16 = dgrad16s(b16.clone(), code, 1, fill)
             chk.equal(lay, "dgrad16s accumulate 16-bit", acc16, (b16.float() + dx32).to(T))
-            acc32 = base.clone()
-            L.check(L.lib.aclgan_conv2d_dgrad16s(C.byref(d_b), code, L.ptr(dy16), L.ptr(w16t), L.ptr(acc32), 0, 1, L.ptr(sscr), L.stream_ptr()), "conv2d_dgrad16s")
+            acc32 = dgrad16s(base.clone(), 0, 1, fill)
             chk(lay, "dgrad16s accumulate fp32", acc32[S].double() - base[S].double(), dx32[S], 1e-5, rows=S)
+            if det:
+                chk.equal(lay, "dgrad16s det rerun", dgrad16s(torch.full((B, Hi, Wi, Ci), NAN, device="cuda"), 0, 0, INF), dx32)
+                chk.equal(lay, "dgrad16s 16-bit det rerun", dgrad16s(torch.full((B, Hi, Wi, Ci), NAN, device="cuda").to(T), code, 0, INF), dx16)
     if w16:
         dy_st = code if s_bwd else 0
         dyw = dy.to(T) if dy_st else dy
         xw = x.to(T) if x_st else x
         _, gw = _ref16(xq, w, b, g, dt, dyq)
         gdb = (dyq if dy_st else dy).double().sum(dim=(0, 1, 2))
-        dw = torch.zeros(Co, k, k, Ci, device="cuda"); db = torch.zeros(Co, device="cuda")      # (the weight gradient accumulates)
-        L.check(L.lib.aclgan_conv2d_wgrad16_st(C.byref(d_b), code, L.ptr(xw), x_st, L.ptr(dyw), dy_st, L.ptr(dw), L.ptr(db),
-                                               L.ptr(_scr(L.lib.aclgan_conv2d_wgrad16_scratch_bytes(C.byref(d_b)))), L.stream_ptr()), "conv2d_wgrad16_st")
+        wnb = L.lib.aclgan_conv2d_wgrad16_scratch_bytes(C.byref(d_b))
+
+        def wgrad16(fill_):
+            dw = torch.zeros(Co, k, k, Ci, device="cuda"); db = torch.zeros(Co, device="cuda")      # (the weight gradient accumulates)
+            L.check(L.lib.aclgan_conv2d_wgrad16_st(C.byref(d_b), code, L.ptr(xw), x_st, L.ptr(dyw), dy_st, L.ptr(dw), L.ptr(db),
+                                                   L.ptr(_scr(wnb, fill_)), L.stream_ptr()), "conv2d_wgrad16_st")
+            return dw, db
+        dw, db = wgrad16(fill)
         chk(lay, "wgrad16 dw (x %s, dy %s)" % ("16" if x_st else "32", "16" if dy_st else "32"), dw, gw, TOL, what="w")
         chk(lay, "wgrad16 db", db, gdb, TOL, what="")
+        if det:
+            dw2, db2 = wgrad16(INF)
+            chk.equal(lay, "wgrad16 dw det rerun", dw2, dw)
+            chk.equal(lay, "wgrad16 db det rerun", db2, db)
 
 
-@pytest.mark.parametrize("wl", ["bf16_256_b8", "fp16_256_b32"])
-def test_16bit_layers_at_launch_shape(L, wl):
+@pytest.mark.parametrize("wl,mode", _modes(["bf16_256_b8", "fp16_256_b32"]), indirect=["mode"])
+def test_16bit_layers_at_launch_shape(L, wl, mode):
     t0 = time.time()
     dt = WL[wl][3]
     _, _, _, _, B = WL[wl]
     cfg, _ = recorded_layers(WL[wl][1], WL[wl][2])
     last = "dec.model.0.model.%d.model.1.conv" % (cfg["gen"]["n_res"] - 1)
-    chk = Check(wl)
+    chk = Check(wl, mode)
     for i, (g, ent) in enumerate(launch_table(wl).items()):
         check_16bit_layer(L, chk, g, ent, dt, 300 + i, any(n.endswith(last) for n in ent["names"]))
     torch.cuda.synchronize()
-    print("\n%s: %d layers in %.1f s" % (wl, len(launch_table(wl)), time.time() - t0))
+    print("\n%s/%s: %d layers in %.1f s" % (wl, mode, len(launch_table(wl)), time.time() - t0))
     chk.done()
 
 
@@ -692,10 +767,12 @@ def _rel64(a, b):
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
 
 
-@pytest.mark.parametrize("B", [3, 4, 8, 32])
-def test_dense_layers_at_step_batches(L, B):
-    """the style MLP (8 -> 256 -> 256 -> 4096, one fused launch), its linear layers forward / backward, the style head (256 -> 8)"""
-    chk = Check("B=%d" % B)
+@pytest.mark.parametrize("B,mode", _modes([3, 4, 8, 32]), indirect=["mode"])
+def test_dense_layers_at_step_batches(L, B, mode):
+    """the style MLP (8 -> 256 -> 256 -> 4096, one fused launch), its linear layers forward / backward, the style head (256 -> 8).  The input
+    gradient of the 256 -> 4096 layer combines O-slices with fp32 atomics in the default plan (misc.hip linear_dx, O >= 512), one slice in
+    the deterministic plan"""
+    chk = Check("B=%d" % B, mode)
     gen = torch.Generator(device="cuda").manual_seed(B)
     S, M, Oo = 8, 256, 4096
     mk = lambda o, i: (torch.randn(o, i, device="cuda", generator=gen) * (2.0 / i) ** 0.5, torch.randn(o, device="cuda", generator=gen) * 0.1)  # noqa: E731
@@ -724,6 +801,12 @@ def test_dense_layers_at_step_batches(L, B):
         chk("linear %dx%d" % (I, Oo_), "bwd dx", dx, xr.grad, TOL, what="")
         chk("linear %dx%d" % (I, Oo_), "bwd dw", dw, wr.grad, TOL, what="")
         chk("linear %dx%d" % (I, Oo_), "bwd db", db, br.grad, TOL, what="")
+        if mode == "det":
+            dx2 = torch.full((B, I), float("nan"), device="cuda"); dw2 = torch.zeros_like(w); db2 = torch.zeros_like(b)
+            L.check(L.lib.aclgan_linear_bwd(B, I, Oo_, L.ptr(x), L.ptr(y), L.ptr(dy.clone()), L.ptr(w), L.ACT[act], L.ptr(dx2), L.ptr(dw2),
+                                            L.ptr(db2), L.stream_ptr()), "linear_bwd")
+            chk.equal("linear %dx%d" % (I, Oo_), "bwd dx,dw,db det rerun", torch.cat([dx2.flatten(), dw2.flatten(), db2]),
+                      torch.cat([dx.flatten(), dw.flatten(), db]))
     chk.done()
 
 
@@ -762,12 +845,12 @@ def test_pooling_at_step_shapes(L, wl):
     chk.done()
 
 
-@pytest.mark.parametrize("wl", ["fp32_256_b8", "fp32_512_b4", "fp16_256_b32", "fp32_256_b3"])
-def test_losses_at_full_pixel_counts(L, wl):
+@pytest.mark.parametrize("wl,mode", _modes(["fp32_256_b8", "fp32_512_b4", "fp16_256_b32", "fp32_256_b3"]), indirect=["mode"])
+def test_losses_at_full_pixel_counts(L, wl, mode):
     """the L1 identity loss, the focus size / digit losses and one multi-term LSGAN launch at the step's pixel counts (up to 32 x 256^2): the
-    multi-block finishes take more partials here than at the operator tests' sizes"""
+    multi-block finishes take more partials here than at the operator tests' sizes (the L1 loss: one workgroup in the deterministic plan)"""
     _, _, S, _, B = WL[wl]
-    chk = Check(wl)
+    chk = Check(wl, mode)
     gen = torch.Generator(device="cuda").manual_seed(7 * S + B)
     npix = B * S * S
     # L1 (x_recon - x): 4-channel decoder output against the 3-channel image
@@ -785,7 +868,7 @@ def test_losses_at_full_pixel_counts(L, wl):
     size, digit = O.focus_losses(decr[:, 3], hp)
     scale = 0.025 / npix / 3
     (scale * (size + digit)).backward()
-    scr = _scr(L.lib.aclgan_focus_loss_scratch_bytes(npix))
+    scr = _scr(L.lib.aclgan_focus_loss_scratch_bytes(npix), NAN if mode == "det" else None)
     slots = torch.zeros(2, device="cuda"); d_dec = torch.zeros(npix, 4, device="cuda")
     L.check(L.lib.aclgan_focus_loss(L.ptr(dec), npix, 0.001, 0.5, 0.3, 0.01, scale, L.ptr(slots), C.c_void_p(slots.data_ptr() + 4), L.ptr(d_dec),
                                     L.ptr(scr), L.stream_ptr()), "focus_loss")

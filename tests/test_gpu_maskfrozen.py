@@ -20,6 +20,7 @@ Blocks are matched between the two implementations by CONTENT, not by order (the
 and runs the discriminators on joint batches): a recorded mask (split into the update's batch-sized chunks) belongs to the oracle
 activation of the same shape it agrees with on >= 99 % of the elements -- unrelated passes agree on ~50 %."""
 import ctypes as C
+import gc
 import os
 
 import pytest
@@ -146,24 +147,32 @@ def _grad_errors(tr, orc, nets_, scale=1.0, floor=1e-3):
     return out
 
 
-def _frozen_and_free(T, dt, B, S, seed, forced=False, cap_bytes=None, d=None):
+def _frozen_and_free(T, dt, B, S, seed, forced=False, cap_bytes=None, d=None, rerun=False, free=True):
     """forced: every eligible convolution through the one-launch Winograd kernel (tuning wino_fused = 2): at B = 2 the cost models keep the
-    4x4 stride-2 layers and the small grids on the direct kernels / the pipeline, so the default run does not reach those kernels"""
+    4x4 stride-2 layers and the small grids on the direct kernels / the pipeline, so the default run does not reach those kernels.
+    The library's plan (default / deterministic) is whatever the caller set; the oracle follows it (_frozen_and_free_impl)"""
     from aclgan_amd import _lib as L
     old = L.lib.aclgan_set_tuning(b"wino_fused", 2) if forced else None
     try:
-        return _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes, d)
+        return _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes, d, rerun, free)
     finally:
         if forced:
             L.lib.aclgan_set_tuning(b"wino_fused", old)
 
 
-def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None):
+def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None, rerun=False, free=True):
     """d: the HIP update runs at batch B made of d distinct samples, each B / d times (the repeated-batch construction of
     tests/test_oracle_repeat_batch_cpu.py), and the oracle runs the d samples alone with focus_delta * k and the loss scale / k.  Its
     own masks then come from the loss graph alone under no_grad (the same activation list, test_forward_only_loss_graph_records_the_
-    update_masks), so there is no masks-free gradient figure"""
+    update_masks), so there is no masks-free gradient figure.
+    In deterministic mode the oracle emulates that plan's 16-bit contract: the input gradient of the sub-pixel layers through the rounded
+    5x5 (compute_dtype(up5_dgrad="plain")) -- every other pass computes the same contract in both plans.
+    rerun: a second trainer from the same state runs the same update (mask recording on, as in the first); res[which]["rerun_differ"] lists
+    the gradient tensors whose bits differ from the first run's.
+    free = False: no masks-free gradient figure either -- the oracle's own masks come from the forward-only loss graph, as with d"""
     from test_oracle_repeat_batch_cpu import batch_map, repeat_batch, rescaled_config, rescaled_loss_scale
+    from aclgan_amd import _lib as L
+    det = L.lib.aclgan_get_deterministic() == 1
     cfg = O.default_config()
     cfg["display_size"] = 1
     cfg["focus_epsilon"] = 0.5      # smooth fixture (tests/golden/make_golden.py: the default 0.01 has a sign discontinuity of 1e4 at m = 0.5)
@@ -181,7 +190,7 @@ def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None):
 
     class ctx:      # the oracle under the build's arithmetic contract (plain fp32, or the emulated 16-bit contract)
         def __enter__(self):
-            self.c = O.compute_dtype(dt, loss_scale=oscale) if dt else None
+            self.c = O.compute_dtype(dt, loss_scale=oscale, up5_dgrad="plain" if det else "merged") if dt else None
             return self.c.__enter__() if self.c else None
 
         def __exit__(self, *a):
@@ -191,6 +200,7 @@ def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None):
     for which, zs, nets_ in (("dis", slice(0, 3), ("dis_A", "dis_B", "dis_2")), ("gen", slice(3, 6), ("gen_AB", "gen_BA"))):
         zz = z[zs]
         tr = _make(T, cfg, nets, dt)
+        assert tr.deterministic == det
         if dt:
             assert tr.grad_scale() == scale
         cap = cap_bytes[which] if cap_bytes else (2 << 30 if S >= 256 else 1 << 29)
@@ -204,9 +214,9 @@ def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None):
             assert st["skipped_gen"] == 0 and st["skipped_dis"] == 0 and st["scale"] == scale and st["clean_updates"] == 1, (which, st)
             assert tr.grad_scale() == scale
         with ctx(), O.act_masks() as rec:                    # the oracle with its OWN masks
-            free = O.OracleTrainer(ocfg, nets=nets)
-            if bmap is None:
-                (free.dis_update if which == "dis" else free.gen_update)(x_a, x_b, zz, apply=False)
+            orc_free = O.OracleTrainer(ocfg, nets=nets)
+            if bmap is None and free:
+                (orc_free.dis_update if which == "dis" else orc_free.gen_update)(x_a, x_b, zz, apply=False)
             else:
                 with torch.no_grad():
                     (O.dis_losses if which == "dis" else O.gen_losses)(nets, x_a, x_b, zz, ocfg)
@@ -217,7 +227,7 @@ def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None):
             (frozen.dis_update if which == "dis" else frozen.gen_update)(x_a, x_b, zz, apply=False)
         assert len(rec2.recorded) == len(rec.recorded)
         e_frozen = _grad_errors(tr, frozen, nets_, scale)
-        e_free = _grad_errors(tr, free, nets_, scale) if bmap is None else None
+        e_free = _grad_errors(tr, orc_free, nets_, scale) if bmap is None and free else None
         print("%s %s_update @%dx%d B=%d%s: %d of %d oracle activations matched to a recorded mask (%d recorded chunks), %d of %d mask elements differ (%.2e)"
               % (dt or "fp32", which, S, S, B, "" if bmap is None else " (%d distinct samples, batch map %s)" % (d, bmap), len(replay),
                  len(rec.recorded), len(chunks), flips, total, flips / max(1, total)))
@@ -232,6 +242,15 @@ def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None):
         ef = torch.tensor([e for e, _, _ in e_frozen], dtype=torch.float64)
         print("   masks FROZEN over all %d gradient tensors: p99 %.2e, mean %.2e" % (len(ef), torch.quantile(ef, 0.99).item(), ef.mean().item()))
         res[which] = dict(frozen=e_frozen, free=e_free, matched=len(replay), acts=len(rec.recorded), unmatched=unmatched, disagree=disagree)
+        if rerun:
+            first = {(n, k): g.detach().clone() for n in nets_ for k, g in getattr(tr, n).named_grads()}
+            del tr
+            gc.collect()      # (a trainer's arena is released when its reference cycles are)
+            tr2 = _make(T, cfg, nets, dt)
+            _hip_update_with_masks(tr2, which, hx_a, hx_b, cfg, hz[zs], B, cap, used=[0])
+            res[which]["rerun_differ"] = [key for key, g in first.items() if not torch.equal(dict(getattr(tr2, key[0]).named_grads())[key[1]], g)]
+            print("   second update from the same state: %d of %d gradient tensors differ in their bits" % (len(res[which]["rerun_differ"]), len(first)))
+            del tr2, first
     return res
 
 
@@ -384,6 +403,30 @@ def test_forward_arena_follows_tuning_changes(T):
         assert max(errs) < 1e-3, (run, errs)
 
 
+def test_forward_workspace_does_not_depend_on_the_mode(T):
+    """the forward-only arena (trainer._ensure_workspace(forward_only=True), what sample() binds) is cached per tuning epoch, and
+    aclgan_set_deterministic does not start a new epoch -- so a mode change must not change what a forward needs.  It does not: the forward
+    kernels' scratch (split-K partials, Winograd and sub-pixel buffers, 16-bit merged filters) is sized for the default plan's largest need
+    whatever the mode.  Pinned at the five single-GPU workloads bench.py times, at their batch and at sample()'s B = 1"""
+    from aclgan_amd import _lib as L
+    from gpu_util import deterministic_mode
+    from test_gpu_launch_shapes import WORKLOADS, _config
+    for wl, yaml_name, S, dt, B in WORKLOADS:
+        tr = T.aclgan_Trainer(_config(yaml_name), compute_dtype=dt)
+        need = {}
+        for det in (False, True):
+            with deterministic_mode(L, det):
+                for b in (1, B):
+                    v = C.c_size_t()
+                    L.check(L.lib.aclgan_forward_workspace_bytes(tr._ctx, b, S, S, C.byref(v)), "forward_workspace_bytes")
+                    need[(det, b)] = v.value
+        print("%s forward-only workspace, default / deterministic: B=1 %d / %d bytes, B=%d %d / %d bytes"
+              % (wl, need[(False, 1)], need[(True, 1)], B, need[(False, B)], need[(True, B)]))
+        for b in (1, B):
+            assert need[(False, b)] > 0 and need[(False, b)] == need[(True, b)], (wl, b, need)
+        del tr
+
+
 # 16-bit: bounds per network group <= 2x the measured value, masks and signs frozen, against the emulated contract.  Measured (round 6,
 # profiles/r06_experiments.md): bf16 dis 7.8e-3, gen.dec 1.82e-2, gen.enc 1.63e-2 (un-frozen: 5.6e-2 / 1.96e-1); fp16 dis 9.2e-4, gen.dec
 # 2.4e-3, gen.enc 2.2e-3 (un-frozen: 2.0e-2 / 7.0e-2) -- what remains is the rounding-flip noise of the 16-bit values themselves
@@ -448,3 +491,40 @@ def test_backward_parity_with_frozen_masks_16bit_benchmarked_batch(T, dt, B):
     assert ndis <= COPY_DISAGREE[dt], (ndis, res["dis"]["disagree"][:8], res["gen"]["disagree"][:8])
     bad = {k: v for k, v in worst.items() if v > min(ETOL_FROZEN_BATCH[dt][k], ETOL_FROZEN[dt][k])}
     assert not bad, bad
+
+
+# Deterministic mode (aclgan_set_deterministic) at the benchmarked batches: the ordered plan -- padded-grid input gradients and folds, the
+# Winograd ring on a zeroed grid, per-slice weight-gradient copies, ordered bias column sums, no split-K -- through the same construction, the
+# same bounds (1e-3 fp32, ETOL_FROZEN_BATCH 16-bit), the oracle under the contract that plan computes.  A second update from the same state
+# must give the same bits.  The fp32 case skips the masks-free oracle gradients (not asserted here; the default-mode case prints them): its
+# oracle masks come from the forward-only loss graph.  (bf16 B=8 is left to the default-mode case above: the suite's time budget.)
+@pytest.mark.parametrize("dt,B", [(None, 8), ("fp16", 32)], ids=["fp32_b8", "fp16_b32"])
+def test_backward_parity_with_frozen_masks_deterministic_benchmarked_batch(T, dt, B):
+    from aclgan_amd import _lib as L
+    from gpu_util import deterministic_mode
+    from test_oracle_repeat_batch_cpu import D_SAMPLES
+    with deterministic_mode(L, True):
+        if dt is None:
+            cap = _mask_capture_bytes(T, 8, 256, 33)
+            res = _frozen_and_free(T, None, 8, 256, 33, cap_bytes=cap, rerun=True, free=False)
+        else:
+            cap = _mask_capture_bytes(T, B, 256, 34, dt)
+            res = _frozen_and_free(T, dt, B, 256, 34, cap_bytes=cap, d=D_SAMPLES, rerun=True)
+    worst, ndis = {}, 0
+    for which in ("dis", "gen"):
+        r = res[which]
+        assert r["matched"] >= (0.3 if which == "dis" else 0.9) * r["acts"], (which, r["matched"], r["acts"], r["unmatched"][:6])
+        assert not r["rerun_differ"], (which, "a second deterministic update gave other bits", r["rerun_differ"][:8])
+        ndis += sum(n for *_, n in r["disagree"])
+        for key, e in _per_net(r["frozen"]).items():
+            kk = "dis" if key.startswith("dis") else "gen" + key[key.index("."):]
+            worst[kk] = max(worst.get(kk, 0.0), e)
+    print("deterministic %s B=%d frozen-mask worst per network group:" % (dt or "fp32", B), {k: "%.2e" % v for k, v in worst.items()},
+          "copy-disagreeing mask elements: %d" % ndis)
+    if dt is None:
+        for which in ("dis", "gen"):
+            assert res[which]["frozen"][0][0] <= 1e-3, (which, res[which]["frozen"][:6])
+    else:
+        assert ndis <= COPY_DISAGREE[dt], (ndis, res["dis"]["disagree"][:8], res["gen"]["disagree"][:8])
+        bad = {k: v for k, v in worst.items() if v > min(ETOL_FROZEN_BATCH[dt][k], ETOL_FROZEN[dt][k])}
+        assert not bad, bad
