@@ -49,9 +49,9 @@ class ImageDesc(C.Structure):
 
 
 ACT = {"none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
-NORM = {"none": 0, "in": 1, "adain": 2, "ln": 3}
+NORM = {"none": 0, "in": 1, "adain": 2, "ln": 3, "sn": 4}
 DTYPE = {"fp32": 0, "bf16": 1, "fp16": 2}
-GROUP_GEN, GROUP_DIS = 0, 1
+GROUP_GEN, GROUP_DIS, GROUP_SN_STATE = 0, 1, 2
 NETS = {"gen_AB": 0, "gen_BA": 1, "dis_A": 2, "dis_B": 3, "dis_2": 4}
 LOSS_NAMES = [
     "loss_gen_adv_A", "loss_gen_adv_B", "loss_gen_adv_2",
@@ -79,6 +79,7 @@ SIGNATURES = {
     "aclgan_get_deterministic": (ci, []),
     "aclgan_last_error": (C.c_char_p, []),
     "aclgan_ctx_create": (ci, [C.POINTER(Arch), C.POINTER(vp)]),
+    "aclgan_ctx_create_dis_norm": (ci, [C.POINTER(Arch), ci, C.POINTER(vp)]),
     "aclgan_ctx_destroy": (None, [vp]),
     "aclgan_ctx_enable_capture": (ci, [vp]),
     "aclgan_warm_streams": (ci, [ci]),
@@ -89,6 +90,10 @@ SIGNATURES = {
     "aclgan_tensor_count": (ci, [vp, ci]),
     "aclgan_tensor_info": (ci, [vp, ci, ci, C.c_char_p, ci, C.POINTER(i64), C.POINTER(ci), C.POINTER(ci)]),
     "aclgan_bind_params": (ci, [vp, ci, vp, vp, vp, vp]),
+    "aclgan_bind_sn_state": (ci, [vp, vp]),
+    "aclgan_sn_scratch_bytes": (sz, [ci, vp, vp]),
+    "aclgan_sn_power_iteration": (ci, [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "aclgan_sn_fold": (ci, [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "aclgan_workspace_bytes": (ci, [vp, ci, ci, ci, C.POINTER(sz)]),
     "aclgan_bind_workspace": (ci, [vp, vp, sz]),
     "aclgan_forward_workspace_bytes": (ci, [vp, ci, ci, ci, C.POINTER(sz)]),

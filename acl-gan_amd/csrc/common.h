@@ -287,4 +287,17 @@ int focus_totals(const float* part, int64_t npix, int nmask, float* totals, hipS
 // Adam under fp16 dynamic loss scaling: overflow scan, update with g/S (or skip), scale update -- all on the device
 int adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, float* state, int group, hipStream_t st);
 
+
+// spectral normalisation (spectral.hip): one power iteration + normalised weight for up to SN_MAX_LAYERS Co x K matrices in four launches;
+// u (Co) is read and overwritten, v (K) overwritten; uf / vf (optional) receive copies of the new u / v, G (optional, Co x K) is zeroed;
+// wn = W / sigma; sigma[l] on the device.  scratch: sn_scratch_bytes.
+const int SN_MAX_LAYERS = 16;
+struct SnLayerPtrs { const float* w; float* u; float* v; float* wn; float* uf; float* vf; float* G; int co, k; };
+size_t sn_scratch_bytes(int n, const int* co, const int* k);
+int sn_power_iteration(int n, const SnLayerPtrs* L, float* sigma, void* scratch, hipStream_t st);
+// grad += G / sigma - (<G, W> / sigma^2) u v^T per layer (u, v, sigma: the ones the forward call used); fixed reduction order
+struct SnFoldPtrs { const float* w; const float* G; const float* u; const float* v; float* grad; int co, k; };
+size_t sn_fold_scratch_bytes(int n, const int* co, const int* k);
+int sn_fold(int n, const SnFoldPtrs* L, const float* sigma, void* scratch, hipStream_t st);
+
 }  // namespace aclgan

@@ -149,6 +149,12 @@ struct StreamPool {
 
 struct aclgan_ctx {
     aclgan_arch arch;
+    // spectral normalisation of the discriminators (aclgan_ctx_create_dis_norm, csrc/spectral.hip): the SN layers of each network in
+    // (scale, layer) order, and their power-iteration state u / v (group ACLGAN_GROUP_SN_STATE: outside Adam, gradients and buckets)
+    int dis_norm = ACLGAN_NORM_NONE;
+    struct SnLayer { int co, k; std::string key; int64_t u_off, v_off; };
+    std::vector<SnLayer> sn_layers[5];
+    Group sn;
     // roctx pass labels: index into pass_names of the pass being built (-1: none); every tape closure remembers the pass that pushed it
     std::vector<std::string> pass_names;
     std::vector<int> tape_pass;
@@ -532,7 +538,10 @@ struct aclgan_ctx {
         op.fn = std::move(fn);
         if (trained >= 0 && groups[trained].grad)
             for (const auto& g : grads)
-                if (g.first && g.second > 0 && op.ng < 4) { op.goff[op.ng] = g.first - groups[trained].grad; op.gnum[op.ng] = g.second; ++op.ng; }
+                // (gradients redirected into arena scratch -- a spectrally normalised layer's per-call weight gradient -- are not ranges of it)
+                if (g.first && g.second > 0 && op.ng < 4 && g.first >= groups[trained].grad && g.first < groups[trained].grad + groups[trained].numel) {
+                    op.goff[op.ng] = g.first - groups[trained].grad; op.gnum[op.ng] = g.second; ++op.ng;
+                }
         op.lane = cur_lane; op.pass = cur_pass_id;
         tape.push_back(std::move(op));
         tape_pass.push_back(cur_pass);
@@ -606,12 +615,31 @@ static void build_gen(Group& g, const std::string& net, const aclgan_arch& a) {
     add_tensor(g, net + "/mlp.model.2.fc.weight", 2, nad, md); add_tensor(g, net + "/mlp.model.2.fc.bias", 1, nad);
 }
 
-static void build_dis(Group& g, const std::string& net, int input_dim, const aclgan_arch& a) {
+// sn (dis.norm: sn): layers 1 .. n_layer-1 of every scale are SpectralNorm(Conv2d) (networks.py:41-43,360-361,567-581): parameters
+// `conv.module.bias` then `conv.module.weight_bar` (the reference's parameters() order once weight is deleted and u / v / bar registered,
+// u and v excluded from dis_opt), their u / v registered in `st`
+static void build_dis(Group& g, const std::string& net, int input_dim, const aclgan_arch& a, std::vector<aclgan_ctx::SnLayer>* sn = nullptr,
+                      Group* st = nullptr) {
     char buf[160];
     for (int s = 0; s < a.dis_num_scales; ++s) {
         int d = a.dis_dim;
         snprintf(buf, sizeof buf, "/cnns.%d.0.conv", s); add_conv(g, net + buf, d, input_dim, 4);
-        for (int i = 0; i < a.dis_n_layer - 1; ++i) { snprintf(buf, sizeof buf, "/cnns.%d.%d.conv", s, i + 1); add_conv(g, net + buf, 2 * d, d, 4); d *= 2; }
+        for (int i = 0; i < a.dis_n_layer - 1; ++i) {
+            snprintf(buf, sizeof buf, "/cnns.%d.%d.conv", s, i + 1);
+            if (sn) {
+                const std::string pre = net + buf + ".module.";
+                add_tensor(g, pre + "bias", 1, 2 * d);
+                add_tensor(g, pre + "weight_bar", 4, 2 * d, d, 4, 4);
+                aclgan_ctx::SnLayer L;
+                L.co = 2 * d; L.k = 16 * d; L.key = std::string(buf + 1) + ".module.";
+                L.u_off = st->numel; add_tensor(*st, pre + "weight_u", 1, L.co);
+                L.v_off = st->numel; add_tensor(*st, pre + "weight_v", 1, L.k);
+                sn->push_back(L);
+            } else {
+                add_conv(g, net + buf, 2 * d, d, 4);
+            }
+            d *= 2;
+        }
         snprintf(buf, sizeof buf, "/cnns.%d.%d", s, a.dis_n_layer); add_conv(g, net + buf, 1, d, 1);
     }
 }
@@ -1114,6 +1142,105 @@ static int decode(aclgan_ctx& c, int net, bool train, Act* content, Act* style, 
     return ACLGAN_OK;
 }
 
+// ---- spectral normalisation (dis.norm: sn; csrc/spectral.hip) ----
+// One discriminator call = one power iteration of every SN layer of the network (reference SpectralNorm.forward -> _update_u_v,
+// networks.py:547-559, before every forward, training or not).  The call's W_bar / sigma goes into a weight slot of its own (the
+// convolution kernels read it unchanged; under a 16-bit compute dtype with its two 16-bit packs), u / v / sigma of the call are kept for
+// the backward, and its convolution weight gradients are redirected into per-call scratch G that the fold closure -- pushed BEFORE the
+// call's layers, so it runs after all of them -- turns into dL/dW_bar += G / sigma - (<G, W_bar> / sigma^2) u v^T.
+struct SnCall {
+    int n = 0;
+    float *slot = nullptr, *G = nullptr, *sigma = nullptr, *uf = nullptr, *vf = nullptr;
+    void* fscr = nullptr;
+    unsigned short *s16 = nullptr, *s16t = nullptr;
+    int64_t soff[SN_MAX_LAYERS] = {}, uoff[SN_MAX_LAYERS] = {}, voff[SN_MAX_LAYERS] = {};
+};
+
+static int sn_begin_call(aclgan_ctx& c, int net, bool train, SnCall* sc) {
+    const std::vector<aclgan_ctx::SnLayer>& Ls = c.sn_layers[net];
+    const int n = (int)Ls.size();
+    if (!c.dry && !c.sn.param) { set_error("spectral norm: aclgan_bind_sn_state was not called"); return ACLGAN_EINVAL; }
+    int co[SN_MAX_LAYERS], kk[SN_MAX_LAYERS], taps[SN_MAX_LAYERS], ci[SN_MAX_LAYERS];
+    int64_t tot = 0, tu = 0, tv = 0;
+    sc->n = n;
+    for (int l = 0; l < n; ++l) {
+        co[l] = Ls[l].co; kk[l] = Ls[l].k; taps[l] = 16; ci[l] = Ls[l].k / 16;
+        sc->soff[l] = tot; sc->uoff[l] = tu; sc->voff[l] = tv;
+        tot += (int64_t)co[l] * kk[l]; tu += co[l]; tv += kk[l];
+    }
+    const bool h16 = c.dtype != ACLGAN_DTYPE_FP32;
+    sc->slot = c.allocf(tot); NEED(sc->slot);
+    if (h16) {
+        sc->s16 = (unsigned short*)c.alloc((size_t)tot * 2); NEED(sc->s16);
+        sc->s16t = (unsigned short*)c.alloc((size_t)tot * 2); NEED(sc->s16t);
+    }
+    sc->sigma = c.allocf(n); NEED(sc->sigma);
+    sc->uf = c.allocf(tu); NEED(sc->uf);
+    sc->vf = c.allocf(tv); NEED(sc->vf);
+    if (train) {
+        sc->G = c.allocf(tot); NEED(sc->G);
+        sc->fscr = c.alloc(sn_fold_scratch_bytes(n, co, kk)); NEED(sc->fscr);
+    }
+    const size_t mark = c.top;
+    void* scr = c.alloc(sn_scratch_bytes(n, co, kk));
+    NEED(scr);
+    SnLayerPtrs P[SN_MAX_LAYERS];
+    for (int l = 0; l < n; ++l) {
+        float* st = c.sn.param;
+        P[l] = SnLayerPtrs{c.param(1, net, Ls[l].key + "weight_bar"), st ? st + Ls[l].u_off : nullptr, st ? st + Ls[l].v_off : nullptr,
+                           sc->slot + sc->soff[l], sc->uf + sc->uoff[l], sc->vf + sc->voff[l], train ? sc->G + sc->soff[l] : nullptr, co[l], kk[l]};
+    }
+    RUN(sn_power_iteration(n, P, sc->sigma, scr, c.st));
+    if (h16) {
+        RUN(cast_flat16(sc->slot, sc->s16, tot, c.dtype, c.st));
+        RUN(transpose_flat16(sc->slot, sc->s16t, sc->soff, co, taps, ci, n, c.dtype, c.st));
+    }
+    c.top = mark;
+    // W read twice, the column partials written and read (1/8 of W), W / sigma written, G zeroed; the 16-bit packs read the slot twice
+    c.count(4.0 * tot * (2.0 + 0.25 + 1.0 + (train ? 1.0 : 0.0)) + (h16 ? (8.0 + 4.0) * tot : 0.0) + 4.0 * 3.0 * (tu + tv));
+    c.exec_flops += 4.0 * tot;       // (two matrix-vector products on the VALU: counted so that the step's FLOP total covers them)
+    if (!train) return ACLGAN_OK;
+    const float* lo = nullptr; const float* hi = nullptr;
+    for (int l = 0; l < n; ++l) {
+        const float* g = c.gradp(1, net, Ls[l].key + "weight_bar");
+        if (!g) continue;
+        if (!lo || g < lo) lo = g;
+        if (!hi || g + (int64_t)co[l] * kk[l] > hi) hi = g + (int64_t)co[l] * kk[l];
+    }
+    aclgan_ctx* cp = &c;
+    const SnCall s = *sc;
+    c.push([=]() -> int {
+        aclgan_ctx& c = *cp;
+        hipStream_t fst = c.st;
+        if (sw(SW_SIDE_STREAM)) {      // a parameter gradient: on the parameter-gradient stream, after this call's weight gradients
+            CHK(c.side_fork());
+            if (!c.dry) fst = c.st2;
+        }
+        SnFoldPtrs F[SN_MAX_LAYERS];
+        for (int l = 0; l < s.n; ++l)
+            F[l] = SnFoldPtrs{c.param(1, net, Ls[l].key + "weight_bar"), s.G + s.soff[l], s.uf + s.uoff[l], s.vf + s.voff[l],
+                              c.gradp(1, net, Ls[l].key + "weight_bar"), co[l], kk[l]};
+        c.count(4.0 * tot * 5.0);      // G twice, W once, dL/dW_bar read and written
+        c.exec_flops += 6.0 * tot;
+        RUN(sn_fold(s.n, F, s.sigma, s.fscr, fst));
+        return ACLGAN_OK;
+    }, {{lo, (int64_t)(hi - lo)}});
+    return ACLGAN_OK;
+}
+
+// the (weight, bias) pair of SN layer `l` of `net` for the current call: W_bar / sigma from the call's slot, the bias as it is; the
+// weight gradient goes into the call's scratch G (the fold adds it into dL/dW_bar)
+static PW sn_pw(aclgan_ctx& c, int net, const SnCall& sc, int l) {
+    const aclgan_ctx::SnLayer& L = c.sn_layers[net][l];
+    PW p;
+    p.w = sc.slot + sc.soff[l];
+    p.dw = sc.G ? sc.G + sc.soff[l] : nullptr;
+    p.nw = (int64_t)L.co * L.k;
+    p.b = c.param(1, net, L.key + "bias"); p.db = c.gradp(1, net, L.key + "bias"); p.nb = L.co;
+    if (sc.s16) { p.w16 = sc.s16 + sc.soff[l]; p.w16t = sc.s16t + sc.soff[l]; }
+    return p;
+}
+
 // MsImageDis.forward (networks.py:50-57)
 // lane_a / lane_b (round 5): the full-resolution scale runs on lane_a, the pooling chain and the two coarser scales on lane_b -- their
 // launches are a quarter / a sixteenth of the first scale's and fill a few CUs each (9 .. 64 workgroups); next to the first scale's
@@ -1125,15 +1252,27 @@ static int dis_forward(aclgan_ctx& c, int net, bool train, Act* x, std::vector<A
     NormSpec none;
     Act* xin = x;
     if (lane_a < 0) lane_a = lane_b = c.cur_lane;
+    // spectral norm: this call's power iteration and normalised weights first, on lane_a; a scale on another lane waits for it
+    SnCall sc;
+    const bool sn = !c.sn_layers[net].empty();
+    int pi_lane = 0, pi_ck = 0;
+    if (sn) {
+        CHK(c.set_lane(lane_a));
+        CHK(c.need(x));
+        CHK(sn_begin_call(c, net, train, &sc));
+        pi_lane = c.cur_lane; pi_ck = c.nck(pi_lane);
+    }
     for (int s = 0; s < a.dis_num_scales; ++s) {
         CHK(c.set_lane(s == 0 ? lane_a : lane_b));
+        if (sn) CHK(c.wait_ck(c.cur_lane, pi_lane, pi_ck));
         Act* h = xin;
         int d = a.dis_dim;
         for (int i = 0; i < a.dis_n_layer; ++i) {
             snprintf(buf, sizeof buf, "cnns.%d.%d.conv", s, i);
             const int co = i == 0 ? d : 2 * d;
+            const PW p = (sn && i > 0) ? sn_pw(c, net, sc, s * (a.dis_n_layer - 1) + i - 1) : c.pw(1, net, buf);
             // (the last layer of a scale feeds the fp32 1x1 head: its output stays fp32)
-            CHK(conv_block(c, c.pw(1, net, buf), train, h, co, 4, 2, 1, 0, ACLGAN_ACT_LRELU, none, nullptr, &h, i + 1 < a.dis_n_layer ? 1 : 0));
+            CHK(conv_block(c, p, train, h, co, 4, 2, 1, 0, ACLGAN_ACT_LRELU, none, nullptr, &h, i + 1 < a.dis_n_layer ? 1 : 0));
             if (i > 0) d *= 2;
         }
         snprintf(buf, sizeof buf, "cnns.%d.%d", s, a.dis_n_layer);
@@ -1427,11 +1566,12 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     PASS(blend(c, dB4, xa, nullptr, &xB, nullptr));                  // trainer.py:110
     CHK(c.set_lane(L1));
     PASS(decode(c, BA, true, c2, z2, &dA4)); CHK(zero_grad_of(c, dA4));   // trainer.py:109
-    PASS(blend(c, dA4, xa, xa, &xA, &pA1, c.new_view(jA, 0, B), c.new_view(jP, 0, B)));   // trainer.py:111,132
+    Act *vA1 = c.new_view(jA, 0, B), *vP1 = c.new_view(jP, 0, B), *vA2 = c.new_view(jA, B, B), *vP2 = c.new_view(jP, B, B);
+    PASS(blend(c, dA4, xa, xa, &xA, &pA1, vA1, vP1));                // trainer.py:111,132
     CHK(c.set_lane(L0));
     PASS(content_encode(c, BA, true, xB, &c3));                      // trainer.py:125
     PASS(decode(c, BA, true, c3, z3, &dA24)); CHK(zero_grad_of(c, dA24)); // trainer.py:127
-    PASS(blend(c, dA24, xB, xa, &xA2, &pA2, c.new_view(jA, B, B), c.new_view(jP, B, B)));   // trainer.py:128,133
+    PASS(blend(c, dA24, xB, xa, &xA2, &pA2, vA2, vP2));              // trainer.py:128,133
     CHK(c.set_lane(L1));
     PASS(decode(c, BA, true, c2, s2, &rA4)); CHK(zero_grad_of(c, rA4));   // trainer.py:113
     CHK(c.set_lane(L2));
@@ -1441,9 +1581,18 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     // adversarial terms (trainer.py:136-139); discriminators frozen.  dis_B only needs x_B_fake: it is enqueued first; each pass runs its
     // full-resolution scale on one lane and the coarser scales on the other
     PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, false, xB, B, {{1.f, 1.f, hp.gan_w, L + ACLGAN_L_GEN_ADV_B}}, L1, LS));
-    PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, jA, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}, {1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
-    PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, jP, B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2},     // networks.py:98: pair_A1 -> 1
-                                                        {0.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));  //                 pair_A2 -> 0
+    if (c.dis_norm != ACLGAN_NORM_SN) {
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, jA, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}, {1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, jP, B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2},     // networks.py:98: pair_A1 -> 1
+                                                            {0.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));  //                 pair_A2 -> 0
+    } else {
+        // spectral norm: every reference call advances u, so each is a pass of its own, in the reference's order (trainer.py:136-139);
+        // one discriminator's calls stay on one lane pair (its power iterations form a chain)
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, vA1, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, vA2, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, vP1, B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, vP2, B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));
+    }
     CHK(c.lanes_join());                                              // the loss kernels below read all of it, on lane 0
     // focus losses (trainer.py:145-161)
     const int64_t npix = (int64_t)B * H * W;
@@ -1554,14 +1703,31 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     PASS(decode(c, BA, false, c2, z2, &dA4));
     PASS(blend(c, dA4, xa, xa, &xA, &pA1, c.new_view(jA, 0, B), c.new_view(jP, 0, B)));
     // calc_dis_loss(fake -> 0, real -> 1) (networks.py:60-67; trainer.py:283-286)
-    PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, jB, B, {{0.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}, {1.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
+    const bool sn = c.dis_norm == ACLGAN_NORM_SN;
+    // spectral norm: one pass per reference call, in the reference's order (calc_dis_loss: fake, then real; trainer.py:283-286), and the
+    // real branch of loss_dis_A twice (each call has its own sigma)
+    if (!sn) PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, jB, B, {{0.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}, {1.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
+    else {
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, c.new_view(jB, 0, B), B, {{0.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, c.new_view(jB, B, B), B, {{1.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
+    }
     CHK(c.set_lane(L0));
     PASS(content_encode(c, BA, false, xB, &c3));
     PASS(decode(c, BA, false, c3, z3, &dA24));
     PASS(blend(c, dA24, xB, xa, &xA2, &pA2, c.new_view(jA, B, B), c.new_view(jP, B, B)));
-    PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, jA, B, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}, {0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A},
-                                                       {1.f, 1.0f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));   // the real branch occurs twice x 0.5
-    PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, jP, B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}, {1.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
+    if (!sn) {
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, jA, B, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}, {0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A},
+                                                           {1.f, 1.0f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));   // the real branch occurs twice x 0.5
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, jP, B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}, {1.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
+    } else {
+        Act* vx = c.new_view(jA, 2 * B, B);
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, c.new_view(jA, 0, B), B, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, vx, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, c.new_view(jA, B, B), B, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, vx, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, c.new_view(jP, 0, B), B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, c.new_view(jP, B, B), B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
+    }
     CHK(c.lanes_join());
     if (!c.dry) {
         hipLaunchKernelGGL(dis_total_kernel, dim3(1), dim3(1), 0, c.st, L, hp);
@@ -1579,20 +1745,30 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
 extern "C" {
 
 int aclgan_ctx_create(const aclgan_arch* arch, aclgan_ctx** out) {
+    return aclgan_ctx_create_dis_norm(arch, ACLGAN_NORM_NONE, out);
+}
+
+int aclgan_ctx_create_dis_norm(const aclgan_arch* arch, int dis_norm, aclgan_ctx** out) {
     ACL_REQUIRE(arch && out, "null argument");
+    ACL_REQUIRE(dis_norm == ACLGAN_NORM_NONE || dis_norm == ACLGAN_NORM_SN, "dis_norm %d: only none (%d) and sn (%d) are implemented", dis_norm,
+                ACLGAN_NORM_NONE, ACLGAN_NORM_SN);
     ACL_REQUIRE(arch->input_dim_a == 3 && arch->input_dim_b == 6, "input_dim_a must be 3 and input_dim_b 6 (trainer.py:19-23,132-133)");
     ACL_REQUIRE(arch->gen_output_dim == 4 || arch->gen_output_dim == 3, "gen.output_dim must be 4 (image + focus mask, trainer.py:108) or 3 (non-focus configuration, trainer.py:117-121)");
     ACL_REQUIRE(arch->gen_dim >= 4 && (arch->gen_dim & (arch->gen_dim - 1)) == 0, "gen.dim must be a power of two >= 4");
     ACL_REQUIRE(arch->dis_dim >= 4 && arch->dis_dim % 4 == 0, "dis.dim must be a multiple of 4");
     ACL_REQUIRE(arch->gen_n_downsample >= 1 && arch->gen_n_res >= 1 && arch->dis_n_layer >= 1 && arch->dis_num_scales >= 1, "bad layer counts");
     ACL_REQUIRE(arch->gen_mlp_dim >= 1 && arch->gen_style_dim >= 1, "bad mlp/style dims");
+    ACL_REQUIRE(dis_norm != ACLGAN_NORM_SN || arch->dis_num_scales * (arch->dis_n_layer - 1) <= SN_MAX_LAYERS,
+                "spectral norm: at most %d normalised layers per discriminator", SN_MAX_LAYERS);
     aclgan_ctx* c = new aclgan_ctx();
     c->arch = *arch;
+    c->dis_norm = dis_norm;
+    const bool sn = dis_norm == ACLGAN_NORM_SN;
     build_gen(c->groups[0], "gen_AB", *arch);
     build_gen(c->groups[0], "gen_BA", *arch);
-    build_dis(c->groups[1], "dis_A", arch->input_dim_a, *arch);
-    build_dis(c->groups[1], "dis_B", arch->input_dim_a, *arch);
-    build_dis(c->groups[1], "dis_2", arch->input_dim_b, *arch);
+    build_dis(c->groups[1], "dis_A", arch->input_dim_a, *arch, sn ? &c->sn_layers[ACLGAN_NET_DIS_A] : nullptr, &c->sn);
+    build_dis(c->groups[1], "dis_B", arch->input_dim_a, *arch, sn ? &c->sn_layers[ACLGAN_NET_DIS_B] : nullptr, &c->sn);
+    build_dis(c->groups[1], "dis_2", arch->input_dim_b, *arch, sn ? &c->sn_layers[ACLGAN_NET_DIS_2] : nullptr, &c->sn);
     for (int g = 0; g < 2; ++g)
         for (const TensorInfo& t : c->groups[g].tensors)
             if (t.ndim == 4) {
@@ -1658,16 +1834,16 @@ int aclgan_bind_loss_scale(aclgan_ctx* ctx, float* state) {
 }
 
 int64_t aclgan_group_numel(const aclgan_ctx* ctx, int group) {
-    if (!ctx || group < 0 || group > 1) return -1;
-    return ctx->groups[group].numel;
+    if (!ctx || group < 0 || group > ACLGAN_GROUP_SN_STATE) return -1;
+    return group == ACLGAN_GROUP_SN_STATE ? ctx->sn.numel : ctx->groups[group].numel;
 }
 int aclgan_tensor_count(const aclgan_ctx* ctx, int group) {
-    if (!ctx || group < 0 || group > 1) return -1;
-    return (int)ctx->groups[group].tensors.size();
+    if (!ctx || group < 0 || group > ACLGAN_GROUP_SN_STATE) return -1;
+    return (int)(group == ACLGAN_GROUP_SN_STATE ? ctx->sn : ctx->groups[group]).tensors.size();
 }
 int aclgan_tensor_info(const aclgan_ctx* ctx, int group, int index, char* name, int name_cap, int64_t* offset, int* shape4, int* ndim) {
-    ACL_REQUIRE(ctx && group >= 0 && group <= 1, "bad ctx/group");
-    const Group& g = ctx->groups[group];
+    ACL_REQUIRE(ctx && group >= 0 && group <= ACLGAN_GROUP_SN_STATE, "bad ctx/group");
+    const Group& g = group == ACLGAN_GROUP_SN_STATE ? ctx->sn : ctx->groups[group];
     ACL_REQUIRE(index >= 0 && index < (int)g.tensors.size(), "tensor index %d out of range", index);
     const TensorInfo& t = g.tensors[index];
     if (name && name_cap > 0) { strncpy(name, t.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
@@ -1681,6 +1857,12 @@ int aclgan_bind_params(aclgan_ctx* ctx, int group, float* param, float* grad, fl
     ACL_REQUIRE(param, "param buffer is null");
     Group& g = ctx->groups[group];
     g.param = param; g.grad = grad; g.m = exp_avg; g.v = exp_avg_sq;
+    return ACLGAN_OK;
+}
+int aclgan_bind_sn_state(aclgan_ctx* ctx, float* state) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(state || ctx->sn.numel == 0, "spectral-norm state buffer is null");
+    ctx->sn.param = state;
     return ACLGAN_OK;
 }
 

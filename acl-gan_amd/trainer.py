@@ -19,7 +19,17 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "hparams_from_config"]
+__all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "dis_norm_from_config", "hparams_from_config"]
+
+DIS_NORMS = ("none", "sn")    # dis.norm values the library implements (sn: SpectralNorm, networks.py:360-361,538-600)
+
+
+def dis_norm_from_config(hp):
+    """dis.norm as the library's ACLGAN_NORM_* code (none -> 0, sn -> ACLGAN_NORM_SN)"""
+    norm = hp["dis"].get("norm", "none")
+    if norm not in DIS_NORMS:
+        raise L.AclganError("dis.norm=%r unsupported (implemented: %s)" % (norm, ", ".join(DIS_NORMS)))
+    return L.NORM[norm]
 
 
 def arch_from_config(hp):
@@ -27,9 +37,10 @@ def arch_from_config(hp):
     for key, want in (("activ", "relu"), ("pad_type", "reflect")):
         if g.get(key, want) != want:
             raise L.AclganError("gen.%s=%r unsupported (only %r is reached by the shipped config)" % (key, g.get(key), want))
-    for key, want in (("activ", "lrelu"), ("pad_type", "reflect"), ("norm", "none"), ("gan_type", "lsgan")):
+    for key, want in (("activ", "lrelu"), ("pad_type", "reflect"), ("gan_type", "lsgan")):
         if d.get(key, want) != want:
             raise L.AclganError("dis.%s=%r unsupported (only %r is reached by the shipped config)" % (key, d.get(key), want))
+    dis_norm_from_config(hp)
     return L.Arch(int(hp["input_dim_a"]), int(hp["input_dim_b"]), int(g["dim"]), int(g["mlp_dim"]), int(g["style_dim"]),
                   int(g["output_dim"]), int(g["n_downsample"]), int(g["n_res"]), int(d["dim"]), int(d["n_layer"]),
                   int(d["num_scales"]))
@@ -100,7 +111,10 @@ class _Net:
                     v.copy_(src)
         for k in self._buffers():
             if k in sd:
-                self._t._dummy_buffers[self.name][k] = sd[k].detach().clone().cpu()
+                self._load_buffer(k, sd[k])
+
+    def _load_buffer(self, key, value):
+        self._t._dummy_buffers[self.name][key] = value.detach().clone().cpu()
 
     def cuda(self, *a, **k):
         return self
@@ -152,7 +166,39 @@ class AdaINGen(_Net):
 
 
 class MsImageDis(_Net):
-    """reference networks.py:21-106 -- forward (list of per-scale maps) on the HIP path."""
+    """reference networks.py:21-106 -- forward (list of per-scale maps) on the HIP path.  Under dis.norm: sn every forward call runs one
+    power iteration of the spectrally normalised layers (u / v advance, networks.py:547-559), as the reference's does."""
+
+    def _sn_entries(self):
+        return [e for e in self._t._tensors.get(L.GROUP_SN_STATE, []) if e["net"] == self.name]
+
+    def _sn_view(self, e):
+        """weight_u as stored; weight_v permuted from the library's (kh, kw, ci) column order to the reference's (ci, kh, kw)"""
+        flat = self._t._sn_state[e["offset"]: e["offset"] + e["numel"]]
+        if e["key"].endswith("weight_v"):
+            ci, kh, kw = e["vshape"]
+            return flat.view(kh, kw, ci).permute(2, 0, 1).reshape(-1)
+        return flat
+
+    def _buffers(self):
+        return OrderedDict((e["key"], self._sn_view(e).clone()) for e in self._sn_entries())
+
+    def load_state_dict(self, sd, strict=True):
+        missing = [e["key"] for e in self._sn_entries() if e["key"] not in sd]
+        if strict and missing:
+            raise L.AclganError("load_state_dict(%s): missing %s" % (self.name, missing))
+        super().load_state_dict(sd, strict=strict)
+
+    def _load_buffer(self, key, value):
+        e = next(e for e in self._sn_entries() if e["key"] == key)
+        src = value.detach().to(device=self._t.device, dtype=torch.float32).reshape(-1)
+        if src.numel() != e["numel"]:
+            raise L.AclganError("load_state_dict(%s): shape mismatch for %s: %s vs (%d,)" % (self.name, key, tuple(value.shape), e["numel"]))
+        if key.endswith("weight_v"):
+            ci, kh, kw = e["vshape"]
+            src = src.view(ci, kh, kw).permute(1, 2, 0).reshape(-1)
+        with torch.no_grad():
+            self._t._sn_state[e["offset"]: e["offset"] + e["numel"]].copy_(src)
 
     def forward(self, x):
         t = self._t
@@ -206,7 +252,7 @@ class aclgan_Trainer:
         self.hip_graph = bool(hg)
         self._graphs = {}
         self._ctx = C.c_void_p()
-        L.check(L.lib.aclgan_ctx_create(C.byref(self.arch), C.byref(self._ctx)), "ctx_create")
+        L.check(L.lib.aclgan_ctx_create_dis_norm(C.byref(self.arch), dis_norm_from_config(hp), C.byref(self._ctx)), "ctx_create")
         L.check(L.lib.aclgan_set_compute_dtype(self._ctx, L.DTYPE[self.compute_dtype]), "set_compute_dtype")
         # the lane scheduler's streams first, before anything else of this process creates one (the rank-0 broadcast below initialises the process
         # group's communicator and its stream): HIP binds streams to hardware queues in creation order (include/aclgan_hip.h, aclgan_warm_streams)
@@ -245,6 +291,19 @@ class aclgan_Trainer:
                 self._w16[grp] = torch.zeros(n, dtype=torch.int16, device=self.device)
                 self._w16t[grp] = torch.zeros(n, dtype=torch.int16, device=self.device)
                 L.check(L.lib.aclgan_bind_params16(self._ctx, grp, L.ptr(self._w16[grp]), L.ptr(self._w16t[grp])), "bind_params16")
+        # spectral norm (dis.norm: sn): u / v of every normalised layer, one flat buffer outside Adam, the gradients and the buckets
+        ents = []
+        for i in range(L.lib.aclgan_tensor_count(self._ctx, L.GROUP_SN_STATE)):
+            L.check(L.lib.aclgan_tensor_info(self._ctx, L.GROUP_SN_STATE, i, name, 256, C.byref(off), shp, C.byref(nd)))
+            net, key = name.value.decode().split("/", 1)
+            ents.append(dict(net=net, key=key, offset=off.value, shape=(shp[0],), numel=shp[0]))
+        for e in ents:     # weight_v: the (ci, kh, kw) of the weight_bar it belongs to
+            if e["key"].endswith("weight_v"):
+                bar = next(t for t in self._tensors[L.GROUP_DIS] if t["net"] == e["net"] and t["key"] == e["key"][:-len("weight_v")] + "weight_bar")
+                e["vshape"] = bar["shape"][1:]
+        self._tensors[L.GROUP_SN_STATE] = ents
+        self._sn_state = torch.zeros(max(1, L.lib.aclgan_group_numel(self._ctx, L.GROUP_SN_STATE)), device=self.device)
+        L.check(L.lib.aclgan_bind_sn_state(self._ctx, L.ptr(self._sn_state)), "bind_sn_state")
         d = self.arch.gen_dim << self.arch.gen_n_downsample
         self._dummy_buffers = {}
         for net in ("gen_AB", "gen_BA"):   # AdaIN running_mean/var: never used, but in the state_dict (networks.py:488-489)
@@ -347,6 +406,9 @@ class aclgan_Trainer:
             if k.endswith("conv.weight") and k.startswith("dec.model.0."):
                 pre = k[: -len("conv.weight")]
                 out += [pre + "norm.running_mean", pre + "norm.running_var"]
+            if k.endswith(".module.weight_bar"):     # SpectralNorm registers u, v, then bar after the conv's bias (networks.py:577-579)
+                pre = k[: -len("weight_bar")]
+                out += [pre + "weight_u", pre + "weight_v"]
             out.append(k)
         assert set(out) == set(pkeys) | set(bkeys), (set(out) ^ (set(pkeys) | set(bkeys)))
         return out
@@ -355,7 +417,17 @@ class aclgan_Trainer:
         for grp, nets in ((L.GROUP_GEN, (self.gen_AB, self.gen_BA)), (L.GROUP_DIS, (self.dis_A, self.dis_B, self.dis_2))):
             for net in nets:
                 for key, v in net.named_parameters():
-                    if key.endswith(".weight"):
+                    if ".module." in key:
+                        # spectrally normalised conv: weights_init skips it (no `weight` attribute after the wrap, utils.py:277), so
+                        # nn.Conv2d's own initialisation stays: kaiming-uniform(a=sqrt 5) weight, bias ~ U(+-1/sqrt(fan_in))
+                        if key.endswith("weight_bar"):
+                            v.copy_(torch.nn.init.kaiming_uniform_(torch.empty(tuple(v.shape)), a=math.sqrt(5.0)).to(self.device))
+                        else:
+                            bar = next(e for e in net._entries if e["key"] == key[: -len("bias")] + "weight_bar")
+                            fan_in = int(math.prod(bar["shape"][1:]))
+                            b = 1.0 / math.sqrt(fan_in)
+                            v.copy_(torch.empty(tuple(v.shape)).uniform_(-b, b).to(self.device))
+                    elif key.endswith(".weight"):
                         fan_in = int(math.prod(v.shape[1:]))
                         if grp == L.GROUP_DIS or kind == "gaussian":
                             w = torch.randn(tuple(v.shape)) * 0.02
@@ -375,6 +447,10 @@ class aclgan_Trainer:
                         v.copy_(torch.rand(tuple(v.shape)).to(self.device))   # networks.py:517
                     else:
                         v.zero_()
+        # u, v ~ N(0, 1), l2-normalised (networks.py:571-574)
+        for e in self._tensors[L.GROUP_SN_STATE]:
+            x = torch.randn(e["numel"], dtype=torch.float64)
+            self._sn_state[e["offset"]: e["offset"] + e["numel"]].copy_((x / (x.norm() + 1e-12)).float().to(self.device))
 
     def _st(self):
         """the current stream of THIS trainer's device (not of torch's current device)"""
@@ -544,6 +620,8 @@ class aclgan_Trainer:
         for grp in (L.GROUP_GEN, L.GROUP_DIS):
             for buf in (self._param[grp], self._m[grp], self._v[grp]):
                 broadcast_flat(buf)
+        if self._tensors[L.GROUP_SN_STATE]:
+            broadcast_flat(self._sn_state)   # spectral norm's u / v (not parameters, but every replica must start from the same)
         steps = torch.tensor([self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls], dtype=torch.int64, device=self.device)
         dist.broadcast(steps, 0)
         self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls = (int(v) for v in steps.tolist())

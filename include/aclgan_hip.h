@@ -46,6 +46,9 @@ extern "C" {
 #define ACLGAN_NORM_IN 1
 #define ACLGAN_NORM_ADAIN 2
 #define ACLGAN_NORM_LN 3
+/* discriminator normalisation (dis.norm, networks.py:41-43,360-361): ACLGAN_NORM_NONE or spectral normalisation (SpectralNorm,
+ * networks.py:538-600) of layers 1 .. n_layer-1 of every scale -- aclgan_ctx_create_dis_norm */
+#define ACLGAN_NORM_SN 4
 
 /* compute dtype of the heavy convolutions (NOT in the reference, which is fp32-only: BASELINE.json configs[2] / [4]).
  * BF16 / FP16: both MFMA operands are rounded to the 16-bit type (round to nearest even), products accumulate in fp32
@@ -58,6 +61,9 @@ extern "C" {
 /* parameter groups = the reference's two optimizers (trainer.py:37-42) */
 #define ACLGAN_GROUP_GEN 0
 #define ACLGAN_GROUP_DIS 1
+/* the power-iteration state of the spectrally normalised layers (weight_u, weight_v: state_dict entries with requires_grad=False, not in
+ * dis_opt): enumerated like a group by aclgan_group_numel / aclgan_tensor_count / aclgan_tensor_info, bound with aclgan_bind_sn_state */
+#define ACLGAN_GROUP_SN_STATE 2
 
 /* networks (trainer.py:19-23) */
 #define ACLGAN_NET_GEN_AB 0
@@ -150,6 +156,12 @@ int aclgan_get_deterministic(void);
 
 /* ---- context: replaces aclgan_Trainer.__init__ network construction (trainer.py:15-23) ---- */
 int aclgan_ctx_create(const aclgan_arch* arch, aclgan_ctx** out);
+/* aclgan_ctx_create with a discriminator normalisation (ACLGAN_NORM_NONE: same as aclgan_ctx_create; ACLGAN_NORM_SN: spectral norm).
+ * Under SN the discriminator group registers `cnns.S.L.conv.module.bias` then `...module.weight_bar` (OIHW, the reference's dis_opt order)
+ * for L = 1 .. n_layer-1, and group ACLGAN_GROUP_SN_STATE holds `...module.weight_u` (Co) and `...module.weight_v` (Ci kh kw, in the
+ * library's (kh, kw, ci) column order: the caller permutes it to the reference's (ci, kh, kw) at the state_dict boundary).  Every
+ * discriminator forward (updates and aclgan_dis_forward) runs one power iteration per SN layer and overwrites u and v. */
+int aclgan_ctx_create_dis_norm(const aclgan_arch* arch, int dis_norm, aclgan_ctx** out);
 void aclgan_ctx_destroy(aclgan_ctx* ctx);
 /* Call once, OUTSIDE any stream capture, on a context whose updates will be captured into a HIP graph (torch.cuda.graph around
  * aclgan_gen_update / aclgan_dis_update).  A captured update runs entirely on the capture stream (one lane, its weight gradients included;
@@ -183,6 +195,18 @@ int aclgan_tensor_info(const aclgan_ctx* ctx, int group, int index, char* name, 
                        int64_t* offset, int* shape4, int* ndim);
 int aclgan_bind_params(aclgan_ctx* ctx, int group, float* param, float* grad, float* exp_avg,
                        float* exp_avg_sq);
+/* the caller-owned buffer of aclgan_group_numel(ctx, ACLGAN_GROUP_SN_STATE) floats (u, v of every SN layer); required under SN */
+int aclgan_bind_sn_state(aclgan_ctx* ctx, float* state);
+/* Spectral normalisation on its own (csrc/spectral.hip), for `n` (<= 16) row-major Co x K matrices packed back to back in w (K % 4 == 0):
+ * one power iteration v = l2n(W^T u), u = l2n(W v), sigma = u . (W v), w_sn = W / sigma (networks.py:547-559); u (sum Co floats) is read
+ * and overwritten, v (sum K) overwritten, sigma[n].  aclgan_sn_fold: grad += G / sigma - (<G, W> / sigma^2) u v^T per matrix -- the
+ * gradient through W / sigma(W) with u, v held constant (g: gradients w.r.t. w_sn, same packing as w).  Fixed reduction order.
+ * scratch: aclgan_sn_scratch_bytes (covers both). */
+size_t aclgan_sn_scratch_bytes(int n, const int* co, const int* k);
+int aclgan_sn_power_iteration(int n, const int* co, const int* k, const float* w, float* u, float* v, float* w_sn, float* sigma,
+                              void* scratch, void* stream);
+int aclgan_sn_fold(int n, const int* co, const int* k, const float* w, const float* g, const float* u, const float* v,
+                   const float* sigma, float* grad, void* scratch, void* stream);
 
 /* ---- reduced-precision compute (ACLGAN_DTYPE_*) ----
  * aclgan_set_compute_dtype: FP32 (default) or BF16 / FP16 for every convolution whose channel counts are multiples of
