@@ -1145,15 +1145,18 @@ static int decode(aclgan_ctx& c, int net, bool train, Act* content, Act* style, 
 // ---- spectral normalisation (dis.norm: sn; csrc/spectral.hip) ----
 // One discriminator call = one power iteration of every SN layer of the network (reference SpectralNorm.forward -> _update_u_v,
 // networks.py:547-559, before every forward, training or not).  The call's W_bar / sigma goes into a weight slot of its own (the
-// convolution kernels read it unchanged; under a 16-bit compute dtype with its two 16-bit packs), u / v / sigma of the call are kept for
-// the backward, and its convolution weight gradients are redirected into per-call scratch G that the fold closure -- pushed BEFORE the
+// convolution kernels read it unchanged; under a 16-bit compute dtype with its two 16-bit packs), the call's sigma is kept for the
+// backward, and its convolution weight gradients are redirected into per-call scratch G that the fold closure -- pushed BEFORE the
 // call's layers, so it runs after all of them -- turns into dL/dW_bar += G / sigma - (<G, W_bar> / sigma^2) u v^T.
+// u and v in the fold are the network's STATE u / v when the backward runs, i.e. as the last call of the update left them, not the
+// call's own: the reference replaces u / v through .data after autograd saved them for sigma = u . (W v) (networks.py:553-559), so its
+// backward of every call reads the last call's vectors (oracle/aclgan_oracle.py: spectral_norm_weight).
 struct SnCall {
     int n = 0;
-    float *slot = nullptr, *G = nullptr, *sigma = nullptr, *uf = nullptr, *vf = nullptr;
+    float *slot = nullptr, *G = nullptr, *sigma = nullptr;
     void* fscr = nullptr;
     unsigned short *s16 = nullptr, *s16t = nullptr;
-    int64_t soff[SN_MAX_LAYERS] = {}, uoff[SN_MAX_LAYERS] = {}, voff[SN_MAX_LAYERS] = {};
+    int64_t soff[SN_MAX_LAYERS] = {};
 };
 
 static int sn_begin_call(aclgan_ctx& c, int net, bool train, SnCall* sc) {
@@ -1165,7 +1168,7 @@ static int sn_begin_call(aclgan_ctx& c, int net, bool train, SnCall* sc) {
     sc->n = n;
     for (int l = 0; l < n; ++l) {
         co[l] = Ls[l].co; kk[l] = Ls[l].k; taps[l] = 16; ci[l] = Ls[l].k / 16;
-        sc->soff[l] = tot; sc->uoff[l] = tu; sc->voff[l] = tv;
+        sc->soff[l] = tot;
         tot += (int64_t)co[l] * kk[l]; tu += co[l]; tv += kk[l];
     }
     const bool h16 = c.dtype != ACLGAN_DTYPE_FP32;
@@ -1175,8 +1178,6 @@ static int sn_begin_call(aclgan_ctx& c, int net, bool train, SnCall* sc) {
         sc->s16t = (unsigned short*)c.alloc((size_t)tot * 2); NEED(sc->s16t);
     }
     sc->sigma = c.allocf(n); NEED(sc->sigma);
-    sc->uf = c.allocf(tu); NEED(sc->uf);
-    sc->vf = c.allocf(tv); NEED(sc->vf);
     if (train) {
         sc->G = c.allocf(tot); NEED(sc->G);
         sc->fscr = c.alloc(sn_fold_scratch_bytes(n, co, kk)); NEED(sc->fscr);
@@ -1188,7 +1189,7 @@ static int sn_begin_call(aclgan_ctx& c, int net, bool train, SnCall* sc) {
     for (int l = 0; l < n; ++l) {
         float* st = c.sn.param;
         P[l] = SnLayerPtrs{c.param(1, net, Ls[l].key + "weight_bar"), st ? st + Ls[l].u_off : nullptr, st ? st + Ls[l].v_off : nullptr,
-                           sc->slot + sc->soff[l], sc->uf + sc->uoff[l], sc->vf + sc->voff[l], train ? sc->G + sc->soff[l] : nullptr, co[l], kk[l]};
+                           sc->slot + sc->soff[l], nullptr, nullptr, train ? sc->G + sc->soff[l] : nullptr, co[l], kk[l]};
     }
     RUN(sn_power_iteration(n, P, sc->sigma, scr, c.st));
     if (h16) {
@@ -1217,9 +1218,10 @@ static int sn_begin_call(aclgan_ctx& c, int net, bool train, SnCall* sc) {
             if (!c.dry) fst = c.st2;
         }
         SnFoldPtrs F[SN_MAX_LAYERS];
+        const float* st = c.sn.param;
         for (int l = 0; l < s.n; ++l)
-            F[l] = SnFoldPtrs{c.param(1, net, Ls[l].key + "weight_bar"), s.G + s.soff[l], s.uf + s.uoff[l], s.vf + s.voff[l],
-                              c.gradp(1, net, Ls[l].key + "weight_bar"), co[l], kk[l]};
+            F[l] = SnFoldPtrs{c.param(1, net, Ls[l].key + "weight_bar"), s.G + s.soff[l], st ? st + Ls[l].u_off : nullptr,
+                              st ? st + Ls[l].v_off : nullptr, c.gradp(1, net, Ls[l].key + "weight_bar"), co[l], kk[l]};
         c.count(4.0 * tot * 5.0);      // G twice, W once, dL/dW_bar read and written
         c.exec_flops += 6.0 * tot;
         RUN(sn_fold(s.n, F, s.sigma, s.fscr, fst));

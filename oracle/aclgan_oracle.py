@@ -125,19 +125,33 @@ def gen_buffer_shapes(g: dict) -> "OrderedDict[str, Tuple[int, ...]]":
 
 
 def dis_param_shapes(input_dim: int, dcfg: dict) -> "OrderedDict[str, Tuple[int, ...]]":
-    """MsImageDis parameters (networks.py:21-48)."""
+    """MsImageDis parameters (networks.py:21-48).  dis.norm sn: layers 1 .. n_layer-1 of every scale are SpectralNorm(Conv2d), whose
+    state_dict holds the conv's bias, then weight_u (Co), weight_v (Ci kh kw) and weight_bar (networks.py:561-581)."""
     out: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    sn = dcfg.get("norm", "none") == "sn"
     for s in range(dcfg["num_scales"]):
         d = dcfg["dim"]
         out["cnns.%d.0.conv.weight" % s] = (d, input_dim, 4, 4)
         out["cnns.%d.0.conv.bias" % s] = (d,)
         for i in range(dcfg["n_layer"] - 1):
-            out["cnns.%d.%d.conv.weight" % (s, i + 1)] = (2 * d, d, 4, 4)
-            out["cnns.%d.%d.conv.bias" % (s, i + 1)] = (2 * d,)
+            if sn:
+                pre = "cnns.%d.%d.conv.module." % (s, i + 1)
+                out[pre + "bias"] = (2 * d,)
+                out[pre + "weight_u"] = (2 * d,)
+                out[pre + "weight_v"] = (d * 16,)
+                out[pre + "weight_bar"] = (2 * d, d, 4, 4)
+            else:
+                out["cnns.%d.%d.conv.weight" % (s, i + 1)] = (2 * d, d, 4, 4)
+                out["cnns.%d.%d.conv.bias" % (s, i + 1)] = (2 * d,)
             d *= 2
         out["cnns.%d.%d.weight" % (s, dcfg["n_layer"])] = (1, d, 1, 1)
         out["cnns.%d.%d.bias" % (s, dcfg["n_layer"])] = (1,)
     return out
+
+
+def is_sn_state(name: str) -> bool:
+    """the power-iteration vectors of a spectrally normalised layer: state, not parameters (requires_grad False, outside Adam)"""
+    return name.endswith((".weight_u", ".weight_v"))
 
 
 def init_params(shapes, kind: str, gen: Optional[torch.Generator] = None) -> Params:
@@ -147,7 +161,10 @@ def init_params(shapes, kind: str, gen: Optional[torch.Generator] = None) -> Par
     reference RNG stream is not required."""
     p: Params = OrderedDict()
     for name, shp in shapes.items():
-        if name.endswith(".weight"):
+        if is_sn_state(name):
+            t = torch.randn(shp, generator=gen)        # SpectralNorm._make_params: N(0, 1), l2-normalised (networks.py:567-574)
+            p[name] = t / (t.norm() + 1e-12)
+        elif name.endswith((".weight", ".weight_bar")):
             fan_in = 1
             for s in shp[1:]:
                 fan_in *= s
@@ -562,14 +579,63 @@ def avgpool3s2(x):
     return F.avg_pool2d(x, 3, stride=2, padding=1, count_include_pad=False)
 
 
+# Per-call sigma log (test infrastructure: tests/test_oracle_sn_cpu.py): inside `with sn_sigmas() as log:` every dis_forward call on a
+# spectrally normalised network appends (id of its parameter dict, [sigma of each SN layer in (scale, layer) order]) to log.calls.
+_SN_LOG = None
+
+
+class sn_sigmas:
+    def __init__(self):
+        self.calls = []
+
+    def __enter__(self):
+        global _SN_LOG
+        self._prev, _SN_LOG = _SN_LOG, self
+        return self
+
+    def __exit__(self, *a):
+        global _SN_LOG
+        _SN_LOG = self._prev
+
+
+def spectral_norm_weight(P: Params, pre: str):
+    """SpectralNorm.forward -> _update_u_v (networks.py:547-559, power_iterations 1): one power iteration on the detached W_bar (viewed
+    as Co x (Ci kh kw)) advances the layer's u / v, then W_bar / sigma with sigma = u . (W_bar v), differentiable in W_bar only.
+    Like the reference, u and v are REPLACED through .data: the tensors autograd saved for sigma are the state tensors themselves, so
+    the backward of every call of an update reads u / v as the LAST call of that network left them (the forward value of sigma is the
+    call's own).  Returns (W_bar / sigma, sigma)."""
+    wb = P[pre + "weight_bar"]
+    u, v = P[pre + "weight_u"], P[pre + "weight_v"]
+    W = wb.reshape(wb.shape[0], -1)
+    with torch.no_grad():
+        t = W.detach().t().mv(u)
+        v.data = t / (t.norm() + 1e-12)
+        y = W.detach().mv(v)
+        u.data = y / (y.norm() + 1e-12)
+    sigma = u.dot(W.mv(v))
+    return wb / sigma, sigma
+
+
 def dis_forward(P: Params, x, dcfg: dict) -> List[torch.Tensor]:
-    """MsImageDis.forward (networks.py:50-57): per scale 4x(4x4 s2 reflect, lrelu) + 1x1."""
+    """MsImageDis.forward (networks.py:50-57): per scale 4x(4x4 s2 reflect, lrelu) + 1x1.  dis.norm sn: layers 1 .. n_layer-1 of
+    every scale convolve with W_bar / sigma (spectral_norm_weight), all power iterations of the call first (they do not depend on x)."""
     outs = []
     nl = dcfg["n_layer"]
+    sn = {}
+    if dcfg.get("norm", "none") == "sn":
+        for s in range(dcfg["num_scales"]):
+            for i in range(1, nl):
+                sn[(s, i)] = spectral_norm_weight(P, "cnns.%d.%d.conv.module." % (s, i))
+        if _SN_LOG is not None:
+            _SN_LOG.calls.append((id(P), [float(sn[k][1].detach()) for k in sorted(sn)]))
     for s in range(dcfg["num_scales"]):
         h = x
         for i in range(nl):
-            h = conv_block(h, P["cnns.%d.%d.conv.weight" % (s, i)], P["cnns.%d.%d.conv.bias" % (s, i)], 2, 1, "lrelu", out16=(i + 1 < nl))
+            if (s, i) in sn:
+                w, b = sn[(s, i)][0], P["cnns.%d.%d.conv.module.bias" % (s, i)]
+            else:
+                w, b = P["cnns.%d.%d.conv.weight" % (s, i)], P["cnns.%d.%d.conv.bias" % (s, i)]
+            h = conv_block(h, w, b, 2, 1, "lrelu", out16=(i + 1 < nl))
         outs.append(F.conv2d(h, P["cnns.%d.%d.weight" % (s, nl)], P["cnns.%d.%d.bias" % (s, nl)]))
         x = avgpool3s2(x)
     return outs
@@ -735,10 +801,11 @@ class OracleTrainer:
                 "dis_B": init_params(dis_param_shapes(hp["input_dim_a"], hp["dis"]), "gaussian", g),
                 "dis_2": init_params(dis_param_shapes(hp["input_dim_b"], hp["dis"]), "gaussian", g),
             }
-        self.nets = {k: OrderedDict((n, t.detach().clone().requires_grad_(True)) for n, t in v.items())
+        # (the spectral-norm u / v stay plain tensors, outside dis_opt, advanced in place by every discriminator call)
+        self.nets = {k: OrderedDict((n, t.detach().clone().requires_grad_(not is_sn_state(n))) for n, t in v.items())
                      for k, v in nets.items()}
         gp = list(self.nets["gen_AB"].values()) + list(self.nets["gen_BA"].values())
-        dp = list(self.nets["dis_A"].values()) + list(self.nets["dis_B"].values()) + list(self.nets["dis_2"].values())
+        dp = [t for n in ("dis_A", "dis_B", "dis_2") for k, t in self.nets[n].items() if not is_sn_state(k)]
         self.gen_opt = AdamState(gp, hp["lr"], hp["beta1"], hp["beta2"], hp["weight_decay"])
         self.dis_opt = AdamState(dp, hp["lr"], hp["beta1"], hp["beta2"], hp["weight_decay"])
         self.sched_calls = 0

@@ -6,10 +6,11 @@ script imports):
     python tests/golden/make_golden_sn.py
 
 Written (data only -- no reference source travels):
-  step_reduced_64_sn_smooth.{json,npz}     reduced width, 64x64, B=2, focus_epsilon 0.5, float64 reference:
+  step_reduced_64_sn_smooth.{json,npz}     reduced width, 64x64, B=2, focus_epsilon 0.5, float64 reference;
+  step_full_64_sn_smooth.{json,npz}        the same at the shipped width (dis.dim 64: SN matrices up to 512 x 4096, gen.dim 64):
       npz: x_a, x_b, z0..z5 (the initial state is tests/sn_nets.py: sn_test_nets(config, seed)),
            uv_dis/<net>/<key>, uv_gen/<net>/<key>   weight_u / weight_v after that update (each from init),
-           seq_uv/<net>/<key>    weight_u / weight_v after the three chained steps
+           seq_uv/<net>/<key>    weight_u / weight_v after the three chained steps (reduced width only)
       json: config, losses (16), grad_stats (sum, norm, max of every gradient of both updates), param_stats_after_dis
             (the discriminator parameters after dis_update + Adam), sigma sequences per update ("sigma_dis" / "sigma_gen": one list per
             discriminator, one entry per forward call, each the sigma of its SN layers in (scale, layer) order, recovered
@@ -90,7 +91,7 @@ def uv(tr, prefix, out):
                 out["%s/%s/%s" % (prefix, net, k)] = v.detach().float().numpy().copy()
 
 
-def run_sn_fixture(cfg, B, H, W, seed, fname):
+def run_sn_fixture(cfg, B, H, W, seed, fname, seq_uv=True):
     dd = torch.float64
     init = sn_test_nets(cfg, seed)
     x_a, x_b, z = G.seeded_inputs(B, H, W, seed)
@@ -147,7 +148,8 @@ def run_sn_fixture(cfg, B, H, W, seed, fname):
         with G.RandnQueue(zd[3:6]):
             tr.gen_update(xa, xb, cfg)
         meta["seq_losses"].append({n: float(getattr(tr, n).detach()) for n in G.LOSS_NAMES_DIS + G.LOSS_NAMES_GEN if hasattr(tr, n)})
-    uv(tr, "seq_uv", out)
+    if seq_uv:      # (the full-width fixture leaves them out: 300 KB of float32 that would bring its npz to the 1 MiB file limit)
+        uv(tr, "seq_uv", out)
 
     np.savez_compressed(os.path.join(HERE, fname + ".npz"), **out)
     json.dump(meta, open(os.path.join(HERE, fname + ".json"), "w"), indent=1, sort_keys=True)
@@ -191,8 +193,16 @@ def checkpoint_fixture_sn():
 
 
 if __name__ == "__main__":
-    key_list_sn()
-    smooth = sn_config(); smooth["focus_epsilon"] = 0.5
-    run_sn_fixture(smooth, 2, 64, 64, 11, "step_reduced_64_sn_smooth")
-    checkpoint_fixture_sn()
+    # python make_golden_sn.py [keys] [reduced] [full] [ckpt]   (no argument: all of them)
+    which = set(sys.argv[1:]) or {"keys", "reduced", "full", "ckpt"}
+    if "keys" in which:
+        key_list_sn()
+    if "reduced" in which:
+        smooth = sn_config(); smooth["focus_epsilon"] = 0.5
+        run_sn_fixture(smooth, 2, 64, 64, 11, "step_reduced_64_sn_smooth")
+    if "full" in which:
+        smooth = sn_config(reduced=False); smooth["focus_epsilon"] = 0.5
+        run_sn_fixture(smooth, 2, 64, 64, 12, "step_full_64_sn_smooth", seq_uv=False)
+    if "ckpt" in which:
+        checkpoint_fixture_sn()
     print("spectral-norm fixtures written to", HERE)

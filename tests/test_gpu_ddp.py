@@ -137,13 +137,24 @@ def test_bucket_callback_fires_after_the_last_writer(lanes):
     without a second GPU: the callback is replaced by exactly that ordering -- event on the compute stream, side stream waits for
     it, side stream snapshots the bucket -- while the backward keeps running; the gradient buffer is poisoned before the update.
     After the update every snapshot must equal the final buffer bit for bit."""
+    _bucket_last_writer(lanes, "none")
+
+
+@pytest.mark.parametrize("lanes", [1, 3])
+def test_bucket_callback_fires_after_the_sn_fold(lanes):
+    """the same with dis.norm sn: the spectral-norm fold (csrc/engine.hip sn_begin_call) is the last writer of every weight_bar gradient --
+    a read-modify-write of the buffer after the call's weight-gradient kernels, pushed with the range of its layers' gradients"""
+    _bucket_last_writer(lanes, "sn")
+
+
+def _bucket_last_writer(lanes, norm):
     import ctypes as C
     import aclgan_amd  # noqa: F401
     from aclgan_amd import _lib as L
     from aclgan_amd.trainer import aclgan_Trainer
     from oracle import aclgan_oracle as O
     cfg = O.default_config()
-    cfg["gen"].update(dim=16, mlp_dim=32, n_res=2); cfg["dis"].update(dim=16); cfg["display_size"] = 1
+    cfg["gen"].update(dim=16, mlp_dim=32, n_res=2); cfg["dis"].update(dim=16, norm=norm); cfg["display_size"] = 1
     g = torch.Generator().manual_seed(41)
     x_a = torch.rand(2, 3, 128, 128, generator=g) * 2 - 1
     x_b = torch.rand(2, 3, 128, 128, generator=g) * 2 - 1

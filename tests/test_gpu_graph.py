@@ -52,3 +52,35 @@ def test_graph_replay_matches_eager(dtype):
     x_a, x_b, z = batches[0]
     tg.dis_update(x_a[:1], x_b[:1], cfg, z=[t[:1] for t in z[:3]])
     assert torch.isfinite(tg.loss_dis_total).item()
+
+
+def test_graph_replay_matches_eager_sn():
+    """dis.norm sn (one pass per discriminator call, the fold as the last writer of the weight_bar gradients): graph replay == eager
+    bit for bit in deterministic mode over the 4 steps -- losses, every parameter and the power-iteration state u / v"""
+    assert torch.cuda.is_available()
+    import aclgan_amd  # noqa: F401
+    from aclgan_amd import trainer as T, _lib as L
+    from sn_nets import sn_test_nets
+    cfg = O.default_config()
+    cfg["gen"].update(dim=16, mlp_dim=32, n_res=2); cfg["dis"].update(dim=16, norm="sn")
+    cfg["display_size"] = 1
+    cfg["focus_epsilon"] = 0.5
+    nets = sn_test_nets(cfg, 0)
+    g = torch.Generator().manual_seed(32)
+    B, S = 2, 64
+    batches = [(torch.rand(B, 3, S, S, generator=g) * 2 - 1, torch.rand(B, 3, S, S, generator=g) * 2 - 1,
+                [torch.randn(B, 8, 1, 1, generator=g) for _ in range(6)]) for _ in range(4)]
+    prev = L.lib.aclgan_get_deterministic()
+    try:
+        te, le, pe = _run(T, cfg, nets, batches, deterministic=True)
+        tg, lg, pg = _run(T, cfg, nets, batches, deterministic=True, hip_graph=True)
+    finally:
+        L.check(L.lib.aclgan_set_deterministic(prev))
+    assert tg.hip_graph, "capture fell back to eager execution"
+    assert tg._graphs["gen"]["graph"] is not None and tg._graphs["dis"]["graph"] is not None
+    assert le == lg, (le, lg)
+    bad = [k for k in pe if not torch.equal(pe[k], pg[k])]
+    assert not bad, bad[:6]
+    assert torch.equal(te._sn_state, tg._sn_state)
+    # u / v moved: 4 steps = 4 x (dis_update + gen_update) calls of every discriminator
+    assert not torch.equal(te.dis_A.state_dict()["cnns.0.1.conv.module.weight_u"].cpu(), nets["dis_A"]["cnns.0.1.conv.module.weight_u"])

@@ -112,30 +112,41 @@ def _hip_update_with_masks(tr, which, x_a, x_b, cfg, z, B, cap_bytes, used=None,
     return (chunks, signs, disagree) if bmap is not None else (chunks, signs)
 
 
-def _match(recorded, chunks):
-    """replay dictionary {oracle activation index: the HIP mask of the same block}; also the flip statistics"""
+def _match(recorded, chunks, exclusive=False):
+    """replay dictionary {oracle activation index: the HIP mask of the same block}; also the flip statistics.
+    exclusive (spectral norm: every reference discriminator call is a pass of its own): each recorded chunk serves one oracle activation,
+    and among the chunks that agree with it on >= 99 % the first one not yet taken wins -- the two real dis_A calls of dis_update see the
+    same x_a with different sigmas, so their masks agree on nearly every element, and the engine runs one network's calls in the
+    reference's order.  used[j]: how many oracle activations took chunk j"""
     by_shape = {}
-    for ch in chunks:
-        by_shape.setdefault(tuple(ch.shape), []).append(ch)
+    for j, ch in enumerate(chunks):
+        by_shape.setdefault(tuple(ch.shape), []).append(j)
     replay, flips, total, unmatched = {}, 0, 0, []
+    used = [0] * len(chunks)
     for i, own in enumerate(recorded):
         cands = by_shape.get(tuple(own.shape), [])
         best, best_agree = None, 0.0
         sub = own.flatten()[::13]
-        for ch in cands:
-            a = (ch.flatten()[::13] == sub).float().mean().item()
+        for j in cands:
+            if exclusive and used[j]:
+                continue
+            a = (chunks[j].flatten()[::13] == sub).float().mean().item()
+            if exclusive and a >= 0.99:
+                best, best_agree = j, a
+                break
             if a > best_agree:
-                best, best_agree = ch, a
+                best, best_agree = j, a
         if best is not None and best_agree >= 0.99:
-            replay[i] = best
-            flips += int((best != own).sum()); total += own.numel()
+            replay[i] = chunks[best]
+            used[best] += 1
+            flips += int((chunks[best] != own).sum()); total += own.numel()
         else:
             unmatched.append((i, tuple(own.shape), round(best_agree, 3)))
-    return replay, flips, total, unmatched
+    return (replay, flips, total, unmatched, used) if exclusive else (replay, flips, total, unmatched)
 
 
 def _grad_errors(tr, orc, nets_, scale=1.0, floor=1e-3):
-    gmax = max(float(t.grad.norm()) for n in nets_ for t in orc.nets[n].values())
+    gmax = max(float(t.grad.norm()) for n in nets_ for t in orc.nets[n].values() if t.grad is not None)     # (SN u / v: no gradient)
     out = []
     for n in nets_:
         for k, gr in getattr(tr, n).named_grads():
@@ -147,20 +158,25 @@ def _grad_errors(tr, orc, nets_, scale=1.0, floor=1e-3):
     return out
 
 
-def _frozen_and_free(T, dt, B, S, seed, forced=False, cap_bytes=None, d=None, rerun=False, free=True):
+def _frozen_and_free(T, dt, B, S, seed, forced=False, cap_bytes=None, d=None, rerun=False, free=True, sn=False):
     """forced: every eligible convolution through the one-launch Winograd kernel (tuning wino_fused = 2): at B = 2 the cost models keep the
     4x4 stride-2 layers and the small grids on the direct kernels / the pipeline, so the default run does not reach those kernels.
     The library's plan (default / deterministic) is whatever the caller set; the oracle follows it (_frozen_and_free_impl)"""
     from aclgan_amd import _lib as L
     old = L.lib.aclgan_set_tuning(b"wino_fused", 2) if forced else None
     try:
-        return _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes, d, rerun, free)
+        return _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes, d, rerun, free, sn)
     finally:
         if forced:
             L.lib.aclgan_set_tuning(b"wino_fused", old)
 
 
-def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None, rerun=False, free=True):
+def _sn_copy(nets):
+    """the oracle advances SN u / v in place: every oracle run starts from a copy of the initial state"""
+    return {k: {n: t.clone() for n, t in v.items()} for k, v in nets.items()}
+
+
+def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None, rerun=False, free=True, sn=False):
     """d: the HIP update runs at batch B made of d distinct samples, each B / d times (the repeated-batch construction of
     tests/test_oracle_repeat_batch_cpu.py), and the oracle runs the d samples alone with focus_delta * k and the loss scale / k.  Its
     own masks then come from the loss graph alone under no_grad (the same activation list, test_forward_only_loss_graph_records_the_
@@ -169,14 +185,22 @@ def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None, rerun=False
     5x5 (compute_dtype(up5_dgrad="plain")) -- every other pass computes the same contract in both plans.
     rerun: a second trainer from the same state runs the same update (mask recording on, as in the first); res[which]["rerun_differ"] lists
     the gradient tensors whose bits differ from the first run's.
-    free = False: no masks-free gradient figure either -- the oracle's own masks come from the forward-only loss graph, as with d"""
+    free = False: no masks-free gradient figure either -- the oracle's own masks come from the forward-only loss graph, as with d
+    sn: dis.norm sn with the seeded SN state of tests/sn_nets.py; recorded chunks are matched exclusively (_match), res[which] also holds
+    "used" (oracle activations per recorded chunk) and "uv" (max |u - u_oracle|, |v - v_oracle| over every SN layer after the update)"""
     from test_oracle_repeat_batch_cpu import batch_map, repeat_batch, rescaled_config, rescaled_loss_scale
     from aclgan_amd import _lib as L
     det = L.lib.aclgan_get_deterministic() == 1
     cfg = O.default_config()
     cfg["display_size"] = 1
     cfg["focus_epsilon"] = 0.5      # smooth fixture (tests/golden/make_golden.py: the default 0.01 has a sign discontinuity of 1e4 at m = 0.5)
-    nets = O.test_nets(cfg, 0)
+    if sn:
+        from sn_nets import sn_test_nets
+        cfg["dis"]["norm"] = "sn"
+        nets = sn_test_nets(cfg, 0)
+    else:
+        nets = O.test_nets(cfg, 0)
+    onets = _sn_copy if sn else (lambda n: n)
     scale = 65536.0 if dt == "fp16" else 1.0
     if d is None:
         x_a, x_b, z = _inputs(B, S, seed)
@@ -219,8 +243,11 @@ def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None, rerun=False
                 (orc_free.dis_update if which == "dis" else orc_free.gen_update)(x_a, x_b, zz, apply=False)
             else:
                 with torch.no_grad():
-                    (O.dis_losses if which == "dis" else O.gen_losses)(nets, x_a, x_b, zz, ocfg)
-        replay, flips, total, unmatched = _match(rec.recorded, chunks)
+                    (O.dis_losses if which == "dis" else O.gen_losses)(onets(nets), x_a, x_b, zz, ocfg)
+        if sn:
+            replay, flips, total, unmatched, used = _match(rec.recorded, chunks, exclusive=True)
+        else:
+            replay, flips, total, unmatched = _match(rec.recorded, chunks)
         sflips = sum(int((a != b).sum()) for a, b in zip(signs, rec.signs))
         with ctx(), O.act_masks(replay, dict(enumerate(signs))) as rec2:             # ... and with the masks / signs of the HIP update
             frozen = O.OracleTrainer(ocfg, nets=nets)
@@ -242,6 +269,15 @@ def _frozen_and_free_impl(T, dt, B, S, seed, cap_bytes=None, d=None, rerun=False
         ef = torch.tensor([e for e, _, _ in e_frozen], dtype=torch.float64)
         print("   masks FROZEN over all %d gradient tensors: p99 %.2e, mean %.2e" % (len(ef), torch.quantile(ef, 0.99).item(), ef.mean().item()))
         res[which] = dict(frozen=e_frozen, free=e_free, matched=len(replay), acts=len(rec.recorded), unmatched=unmatched, disagree=disagree)
+        if sn:
+            uv = 0.0
+            for n in ("dis_A", "dis_B", "dis_2"):
+                for k, t in getattr(tr, n).state_dict().items():
+                    if O.is_sn_state(k):
+                        uv = max(uv, (t.cpu().double() - frozen.nets[n][k].double()).abs().max().item())
+            res[which].update(used=used, chunks=len(chunks), uv=uv)
+            print("   SN: recorded chunks taken by 0 / 1 / >1 oracle activations: %d / %d / %d; max |u, v - oracle| %.2e"
+                  % (used.count(0), used.count(1), sum(1 for x in used if x > 1), uv))
         if rerun:
             first = {(n, k): g.detach().clone() for n in nets_ for k, g in getattr(tr, n).named_grads()}
             del tr
@@ -310,13 +346,19 @@ def test_frozen_mask_cases_reach_the_stride2_phases(T):
         assert on < off, (key, on, off)
 
 
-def _mask_capture_bytes(T, B, S, seed, dt=None):
+def _mask_capture_bytes(T, B, S, seed, dt=None, sn=False):
     """mask-recording buffer for an update at batch B under compute dtype dt: the bytes the same update takes at B = 2
-    (aclgan_debug_mask_info's offsets; every recorded mask is a multiple of the batch), scaled by B / 2, plus 10 % and 64 MB of margin"""
+    (aclgan_debug_mask_info's offsets; every recorded mask is a multiple of the batch), scaled by B / 2, plus 10 % and 64 MB of margin.
+    sn: with spectrally normalised discriminators (one pass per reference call: dis_update records the real dis_A branch twice)"""
     cfg = O.default_config()
     cfg["display_size"] = 1
     cfg["focus_epsilon"] = 0.5
-    nets = O.test_nets(cfg, 0)
+    if sn:
+        from sn_nets import sn_test_nets
+        cfg["dis"]["norm"] = "sn"
+        nets = sn_test_nets(cfg, 0)
+    else:
+        nets = O.test_nets(cfg, 0)
     x_a, x_b, z = _inputs(2, S, seed)
     out = {}
     for which, zz in (("dis", z[:3]), ("gen", z[3:])):
