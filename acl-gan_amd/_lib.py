@@ -48,6 +48,13 @@ class ImageDesc(C.Structure):
         "src_h", "src_w", "res_h", "res_w", "crop_y", "crop_x", "flip", "tab_x", "tab_y", "ksize_x", "ksize_y")]
 
 
+GRID_MAX_SRCS = 16      # ACLGAN_GRID_MAX_SRCS
+
+
+class GridSrc(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("bstride", C.c_int64), ("n", C.c_int), ("channels", C.c_int)]
+
+
 ACT = {"none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
 NORM = {"none": 0, "in": 1, "adain": 2, "ln": 3, "sn": 4}
 DTYPE = {"fp32": 0, "bf16": 1, "fp16": 2}
@@ -175,6 +182,8 @@ SIGNATURES = {
     "aclgan_image_resample_ksize": (ci, [ci, ci]),
     "aclgan_image_resample_coeffs": (ci, [ci, ci, C.POINTER(ci), C.POINTER(ci)]),
     "aclgan_image_batch_transform": (ci, [vp, C.POINTER(ImageDesc), vp, ci, vp, vp, ci, ci, vp]),
+    "aclgan_image_grid_scratch_bytes": (sz, []),
+    "aclgan_image_grid_u8": (ci, [C.POINTER(GridSrc), ci, ci, ci, ci, vp, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

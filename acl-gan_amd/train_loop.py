@@ -55,3 +55,10 @@ def snapshot_due(iterations, config):
 def log_due(iterations, config):
     """train.py:77-80"""
     return (iterations + 1) % config["log_iter"] == 0
+
+
+def image_due(iterations, config, key):
+    """train.py:83,92: key is "image_save_iter" or "image_display_iter"; a config without the key, or with a value <= 0, never
+    writes pictures"""
+    every = config.get(key) or 0
+    return every > 0 and (iterations + 1) % every == 0

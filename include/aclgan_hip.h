@@ -572,6 +572,26 @@ int aclgan_image_resample_coeffs(int in_size, int out_size, int* bounds, int* co
 int aclgan_image_batch_transform(const void* src, const aclgan_image_desc* descs_host, const void* descs_dev, int n,
                                  const void* tables_dev, float* out, int out_h, int out_w, void* stream);
 
+/* ---- sample pictures while training (reference train.py:83-95 -> utils.py:115-124 __write_images / write_2images, under the
+ * torchvision 0.4.0 its acl-gan.yaml pins): the tuple trainer.sample() returns -> ONE uint8 picture, on the device ----
+ * K fp32 NCHW tensors (n_k, C_k, H, W), C_k in {1, 3}; every image's C_k*H*W block dense, `bstride` floats between consecutive
+ * images (so channel slices of a decoder output need no copy).  Semantics = expand(-1, 3, -1, -1) of the 1-channel tensors, cat along
+ * the batch (N = sum n_k), make_grid(nrow, padding=0, normalize=True): ONE global lo = min, hi = max over all values, clamp(x, lo,
+ * hi), (x - lo) / d with d = fp32(double(hi) - double(lo) + 1e-5) and a true fp32 division; cols = min(nrow, N), rows = ceil(N /
+ * cols), image n in cell (n / cols, n % cols), cells past N zero; then save_image's v * 255, + 0.5 (two separately rounded fp32
+ * operations), clamp to [0, 255], truncation to uint8.  out: device uint8 [rows*H][cols*W][3] (HWC RGB), every byte written.
+ * The bytes equal the fp32 CPU evaluation of that rule exactly.  lo / hi stay on the device (scratch: aclgan_image_grid_scratch_bytes()
+ * bytes, 4-byte aligned, contents irrelevant); two launches on `stream`, no host synchronisation.  NaN / Inf inputs do not fault;
+ * the pixels they produce are unspecified.  `srcs` is a HOST array, read before the call returns. */
+#define ACLGAN_GRID_MAX_SRCS 16
+typedef struct aclgan_grid_src {
+    const float* data;       /* device */
+    int64_t bstride;         /* floats between image i and image i + 1 */
+    int n, channels;
+} aclgan_grid_src;
+size_t aclgan_image_grid_scratch_bytes(void);
+int aclgan_image_grid_u8(const aclgan_grid_src* srcs, int K, int H, int W, int nrow, uint8_t* out, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

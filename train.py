@@ -9,8 +9,13 @@ batches come from the device input pipeline (acl-gan_amd/data.py: host decode, O
 flip/Resize/crop/ToTensor/Normalize, bit-identical to the reference's torchvision/PIL chain, utils.py:43-100)
 and are zipped exactly like train.py:66; with --synthetic, synthetic U(-1,1) images of the configured crop size
 are used instead.  A configured dataset that does not exist is an error (as in the reference), never a silent
-fallback to noise.  Out of scope: the TensorBoard/HTML writers.  Losses are printed
-every log_iter iterations with ONE device->host copy of the 16-entry loss array instead of 16 (.item() each).
+fallback to noise.  Losses are printed
+every log_iter iterations with ONE device->host copy of the 16-entry loss array instead of 16 (.item() each); the same copy feeds
+logs/<model>/losses.csv (the reference logs the same members to TensorBoard, train.py:78-80).
+
+Pictures (train.py:44-47,83-95): every image_save_iter iterations trainer.sample() runs on fixed test and train display images and
+outputs/<model>/images/gen_a2b_{test,train}_%08d.jpg and outputs/<model>/index.html are written; every image_display_iter iterations
+images/gen_a2b_train_current.jpg.  The picture is composed on the device (acl-gan_amd/visual.py, csrc/grid.hip); the host encodes the JPEG.
 
 Data parallel (not in the reference, which is single-GPU: train.py:42): launched as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 train.py --config ...
@@ -85,6 +90,7 @@ def main():
     model_name = os.path.splitext(os.path.basename(opts.config))[0]
     output_directory = os.path.join(opts.output_path, "outputs", model_name)
     checkpoint_directory = os.path.join(output_directory, "checkpoints")
+    image_directory = os.path.join(output_directory, "images")
     if is_main:
         os.makedirs(checkpoint_directory, exist_ok=True)
         shutil.copy(opts.config, os.path.join(output_directory, "config.yaml"))   # train.py:61
@@ -126,7 +132,7 @@ def main():
             sys.exit("training images not found (%r): fix data_root / data_folder_train_a in %s, or pass --synthetic "
                      "to train on synthetic U(-1,1) batches" % (folder, opts.config))
         from aclgan_amd.data import get_all_data_loaders
-        train_loader_a, train_loader_b, _, _ = get_all_data_loaders(config, device="cuda:%d" % local_rank, rank=rank, world_size=world)   # train.py:43
+        train_loader_a, train_loader_b, test_loader_a, test_loader_b = get_all_data_loaders(config, device="cuda:%d" % local_rank, rank=rank, world_size=world)   # train.py:43
         if iterations and len(train_loader_a) and len(train_loader_b):           # resumed: do not replay the permutations of the epochs already seen
             # (recorded count; a checkpoint directory written before round 5 has none: every earlier epoch is then assumed complete)
             done = int(loop_state.get("epoch", iterations // min(len(train_loader_a), len(train_loader_b))))
@@ -136,7 +142,18 @@ def main():
         batches_per_pass = max(1, min(len(train_loader_a), len(train_loader_b)))
         if is_main:
             print("data: %d / %d training images, device input pipeline, %d rank(s) x batch %d" % (len(train_loader_a.source), len(train_loader_b.source), world, B))
-    from aclgan_amd.train_loop import run_epochs, snapshot_due, log_due
+    from aclgan_amd.train_loop import run_epochs, snapshot_due, log_due, image_due
+    from aclgan_amd import visual
+    display_size = config["display_size"]
+    loss_log = visual.LossLog(os.path.join(opts.output_path, "logs", model_name, "losses.csv")) if is_main else None
+    display = None
+    if is_main and any((config.get(k) or 0) > 0 for k in ("image_save_iter", "image_display_iter")):
+        # train.py:44-47: fixed display images, fetched without moving any generator the training reads
+        if opts.synthetic:
+            dgen = torch.Generator().manual_seed(99991 + seed)
+            display = [(torch.rand(display_size, 3, H, W, generator=dgen) * 2 - 1).cuda() for _ in range(4)]
+        else:
+            display = [visual.display_stack(l.dataset, display_size) for l in (train_loader_a, train_loader_b, test_loader_a, test_loader_b)]
     clock = {"t0": time.time()}
 
     def on_iteration(info):      # train.py:78-99: log / snapshot, between the updates and the learning-rate step
@@ -147,6 +164,19 @@ def main():
             print("Iteration: %08d/%08d  %.3fs/it  " % (iterations + 1, max_iter, time.time() - clock["t0"]) +
                   " ".join("%s=%.4g" % (n[5:], float(vals[i])) for i, n in enumerate(L.LOSS_NAMES)
                            if n in ("loss_gen_total", "loss_dis_total", "loss_idt_A", "loss_gen_adv_A")))
+            loss_log.append(iterations + 1, vals.tolist())
+        if display is not None and image_due(iterations, config, "image_save_iter"):      # train.py:83-90
+            train_a, train_b, test_a, test_b = display
+            with torch.no_grad():
+                test_image_outputs = trainer.sample(test_a, test_b)
+                train_image_outputs = trainer.sample(train_a, train_b)
+            visual.write_2images(test_image_outputs, display_size, image_directory, "test_%08d" % (iterations + 1))
+            visual.write_2images(train_image_outputs, display_size, image_directory, "train_%08d" % (iterations + 1))
+            visual.write_html(os.path.join(output_directory, "index.html"), iterations + 1, config["image_save_iter"], "images")
+        if display is not None and image_due(iterations, config, "image_display_iter"):   # train.py:92-95
+            with torch.no_grad():
+                image_outputs = trainer.sample(display[0], display[1])
+            visual.write_2images(image_outputs, display_size, image_directory, "train_current")
         if is_main and snapshot_due(iterations, config):      # replicas are identical: rank 0's copy is THE checkpoint
             trainer.save(checkpoint_directory, iterations)
             # "epoch": the pass a resumed run starts with -- the NEXT one when this snapshot falls on the last batch of a pass (a resume used to
