@@ -765,9 +765,12 @@ class AdamState:
         self.t = 0
 
     @torch.no_grad()
-    def step(self, grads: List[torch.Tensor], lr: Optional[float] = None):
+    def step(self, grads: List[torch.Tensor], lr: Optional[float] = None, t: Optional[int] = None):
+        """t: the bias-correction step of this update (default: one more than the last; oracle/optimizer_oracle.py passes the
+        number of APPLIED updates when a loss scaler skips some)."""
         lr = self.lr if lr is None else lr
-        self.t += 1
+        self.t = self.t + 1 if t is None else int(t)
+        assert self.t >= 1
         bc1 = 1 - self.b1 ** self.t
         bc2 = 1 - self.b2 ** self.t
         for p, g, m, v in zip(self.params, grads, self.m, self.v):

@@ -224,6 +224,25 @@ def test_fp16_overflow_skips_the_update_and_halves_the_scale(T):
     assert st["skipped_dis"] == 1 and st["clean_updates"] == 1 and st["scale"] == 1024.0
     d = (tr._param[1] - p0).abs().max().item()
     assert 0 < d <= 1.01 * cfg["lr"]            # |first Adam step| <= lr holds only if bias correction used step = 1
+    # ... which the line above cannot tell: with betas (0.5, 0.999) a first applied update computed with step 2 moves a parameter by
+    # 0.9426 lr (step 3: 0.9892 lr), inside that bound.  The discriminating checks: some parameter moves by (nearly) the full lr, and
+    # p, m, v equal the fp64 model (oracle/optimizer_oracle.py) run with bias-correction step 1 on the gradients the buffer holds,
+    # within twice the error torch's own fp32 Adam has on the same inputs (the bound of tests/test_gpu_optimizer.py).
+    assert d >= 0.97 * cfg["lr"], d
+    from oracle import optimizer_oracle as M
+    S = tr.grad_scale("dis")
+    assert S == 1024.0
+    g = (tr._grad[1] / S).cpu()
+    o = tr._opt[1]
+    hyper = [M.f32(o[k]) for k in ("beta1", "beta2", "eps", "weight_decay")]
+    lr = M.f32(cfg["lr"])
+    a64 = M.Adam64(p0.cpu(), *hyper); a64.step(g, lr, t=1)
+    t32 = M.TorchAdam32(p0.cpu(), *hyper); t32.step(g, lr)
+    e_ref = M.parity_metrics(t32.p, t32.m, t32.v, a64, lr, 1)
+    e_hip = M.parity_metrics(tr._param[1].cpu(), tr._m[1].cpu(), tr._v[1].cpu(), a64, lr, 1)
+    print("first applied update after the skip vs the fp64 model with step 1: HIP", e_hip, "torch fp32", e_ref)
+    bad = {k: (e_hip[k], e_ref[k]) for k in M.METRICS if not e_hip[k] <= 2 * e_ref[k]}
+    assert not bad, bad
 
 
 @pytest.mark.parametrize("dt", ["bf16", "fp16"])
