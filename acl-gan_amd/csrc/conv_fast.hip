@@ -263,7 +263,7 @@ int launch_fwd_fast(const ConvGeom& g, FwdFP p, hipStream_t st) {
 // ------------------------------------------------------------------------------------------
 
 template <int WM, int WN, int TM, int TN>
-__global__ void __launch_bounds__(WM * WN * 64) conv_dgrad_fast_kernel(DgFP pk) {
+__global__ void __launch_bounds__(WM * WN * 64) conv_dgrad_fast_kernel(DgFP p) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
     constexpr int RP = NT / 4;
     constexpr int A_IT = BM / RP;
@@ -280,15 +280,9 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_dgrad_fast_kernel(DgFP pk) 
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    const int tile = xcd_map(blockIdx.x, pk.nwg);
-    int m0 = (tile / pk.tiles_n) * BM;
-    const int n0 = (tile % pk.tiles_n) * BN;
-    DgFP p = pk;                               // local copy: mode 3 resolves to 1 (interior tile) or 2 (halo tile) per workgroup
-    if (pk.mode == 3) {
-        const int tm = tile / pk.tiles_n;
-        if (tm >= pk.Ti) { p.mode = 2; m0 = (tm - pk.Ti) * BM; } else p.mode = 1;
-    }
-    const bool merged = pk.mode == 3;
+    const int tile = xcd_map(blockIdx.x, p.nwg);
+    const int m0 = (tile / p.tiles_n) * BM;
+    const int n0 = (tile % p.tiles_n) * BN;
     const int cls = blockIdx.z / p.ksplit, slice = blockIdx.z - cls * p.ksplit;
     const int cy = cls / p.s, cx = cls % p.s;
     const int Tx = (p.k - cx + p.s - 1) / p.s, Ty = (p.k - cy + p.s - 1) / p.s;
@@ -317,8 +311,6 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_dgrad_fast_kernel(DgFP pk) 
             if (py < p.Hp && px < p.Wp) {
                 if (p.mode == 0 || p.ringpad) oo = (b * p.Hp + py) * p.Wp + px;
                 else oo = (b * p.Hd + (refl(py - p.pad, p.Hi) >> p.upshift)) * p.Wd + (refl(px - p.pad, p.Wi) >> p.upshift);   // mode 1: identity inside
-                // merged launch: interior pixels that also receive mirrored halo rows are combined with atomics (bit 30)
-                if (merged && p.mode == 1 && (dg_is_target(py - p.pad, p.Hi, p.pad) || dg_is_target(px - p.pad, p.Wi, p.pad))) oo |= 1 << 30;
             }
         }
         ri_o[r] = oo;
@@ -428,9 +420,8 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_dgrad_fast_kernel(DgFP pk) 
             for (int r = 0; r < 16; ++r) {
                 const int of = ri_o[wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh];
                 if (of >= 0) {
-                    const int oo = of & ~(1 << 30);
-                    float* o = p.dxp + (size_t)oo * p.Ci + n;
-                    if (p.ksplit > 1 || (p.mode == 2 && !p.ringpad) || (of >> 30)) atomicAdd(o, acc[i][j][r]);   // split-K partials / mirrored halo / its targets
+                    float* o = p.dxp + (size_t)of * p.Ci + n;
+                    if (p.ksplit > 1 || (p.mode == 2 && !p.ringpad)) atomicAdd(o, acc[i][j][r]);   // split-K partials / mirrored halo
                     else if (p.accumulate) *o += acc[i][j][r];
                     else *o = acc[i][j][r];
                 }
@@ -465,7 +456,6 @@ int launch_dgrad_fast(const ConvGeom& g, DgFP p, hipStream_t st) {
     const int nk_plan = (p.mode == 2 && p.band == 0) ? std::max(g.Co / 16, nk_min / ((g.k + g.s - 1) / g.s)) : nk_min;
     if (nblk < 128 && nk_plan >= 32 && !sw(SW_DETERMINISTIC) && !p.ringpad)       // (the slices combine with fp32 atomics; ringpad: one plain store per position)
         p.ksplit = max(1, min(nk_plan / 8, 512 / nblk));   // floor: stay within one round of 512 resident workgroups
-    if (p.mode == 2 && p.band == 0 && !p.ringpad && !sw(SW_DETERMINISTIC) && sw(SW_HALO_SPLIT) > 0) p.ksplit = std::min(sw(SW_HALO_SPLIT), nk_plan);
     if (p.ksplit > 1 && p.mode == 0) {
         hipError_t e = hipMemsetAsync(p.dxp, 0, conv_dgrad_scratch_bytes(g), st);
         if (e != hipSuccess) return hip_fail(e, "memset dxp");
@@ -479,57 +469,16 @@ int launch_dgrad_fast(const ConvGeom& g, DgFP p, hipStream_t st) {
     return ACLGAN_OK;
 }
 
-// interior + halo ring in ONE launch (mode 3).  Returns EUNSUPPORTED when the grid is so small that the split-K two-launch
-// path is the better plan.  The separate halo launch is 34 x 15 workgroups with a full k loop: 48 us of a 354 us ResBlock dgrad
-// (fp32), 36 of 116 us (bf16); as 17 extra M-tiles of the interior launch it is only +6 % work -- but see the measurement below.
-template <int WM, int WN, int TM, int TN>
-int launch_dgrad_fast_merged(const ConvGeom& g, DgFP p, hipStream_t st) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    // OPT-IN (ACLGAN_MERGEDHALO=1).  Measured (profiles/r02_experiments.md): correct, but slower -- the 34 halo tiles are a second,
-    // nearly empty round after the 512 interior workgroups (one full tile duration of tail), and the divergent atomic/plain
-    // epilogue of the interior tiles costs more than the 36-48 us launch it removes: fp32 step 171.7 -> 182.5 ms.
-    if (!sw(SW_MERGEDHALO) || sw(SW_DETERMINISTIC) || g.p == 0 || g.Ci % 4 != 0) return ACLGAN_EUNSUPPORTED;
-    int mi = 0, mh = 0;
-    for (int cy = 0; cy < g.s; ++cy)
-        for (int cx = 0; cx < g.s; ++cx) {
-            const int ylo = g.p > cy ? (g.p - cy + g.s - 1) / g.s : 0, xlo = g.p > cx ? (g.p - cx + g.s - 1) / g.s : 0;
-            const int yhi = std::min(p.Hc - 1, (g.p + g.Hi - 1 - cy) / g.s), xhi = std::min(p.Wc - 1, (g.p + g.Wi - 1 - cx) / g.s);
-            const int inner = std::max(0, yhi - ylo + 1) * std::max(0, xhi - xlo + 1);
-            mi = std::max(mi, g.B * inner); mh = std::max(mh, g.B * (p.Hc * p.Wc - inner));
-        }
-    if (mi <= 0 || mh <= 0) return ACLGAN_EUNSUPPORTED;
-    p.tiles_n = cdiv(g.Ci, BN);
-    p.Ti = cdiv(mi, BM);
-    p.nwg = (p.Ti + cdiv(mh, BM)) * p.tiles_n;
-    const int nk_min = ((g.k + g.s - 1) / g.s) * ((g.k + g.s - 1) / g.s) * (g.Co / 16);
-    if (p.nwg * g.s * g.s < 128 && nk_min >= 32) return ACLGAN_EUNSUPPORTED;       // small grid: split-K pays more
-    p.ksplit = 1; p.mode = 3; p.Mc = mi;
-    if (!p.accumulate) {
-        const int64_t n = (int64_t)g.B * (2 * g.p * g.Wi + 2 * g.p * g.Hi) * (g.Ci / 4);
-        hipLaunchKernelGGL(dg_frame_zero_kernel, dim3((int)std::min<int64_t>(cdiv64(n, 256), 2048)), dim3(256), 0, st, p.dxp, g.B, g.Hi, g.Wi, g.Ci, g.p);
-        ACL_CHECK_LAUNCH("dg_frame_zero_kernel");
-    }
-    hipLaunchKernelGGL((conv_dgrad_fast_kernel<WM, WN, TM, TN>), dim3(p.nwg, 1, g.s * g.s), dim3(WM * WN * 64), 0, st, p);
-    ACL_CHECK_LAUNCH("conv_dgrad_fast_kernel(merged)");
-    return ACLGAN_OK;
-}
-
 // the halo ring of a reflection-padded layer (mode 2): its GEMM is short and wide (3x3 ResBlock layer at 64x64 B=8: 2 016 ring rows x 256 x 768
 // useful k) and latency-bound -- a single 128 x 128 slice takes 2.7 us per 16-channel k-tile, three times its MFMAs.  Measured on that layer
-// (kernel trace of the operator, scripts/r06/gpu15.sh; tile x split count): 128 x 128: 131 / 74.5 / 54.2 / 45.9 / 38.5 us with 1 / 2 / 3 / 4 / 6
+// (kernel trace of the operator, profiles/r06_halo_tile_split_sweep.txt; tile x split count): 128 x 128: 131 / 74.5 / 54.2 / 45.9 / 38.5 us with 1 / 2 / 3 / 4 / 6
 // slices; 64 x 64: 54.7 (1) / 39.3 (2) / 35.0 (3); 64 x 128: **34.3** (planned: 6) / 36.4 (3); 128 x 64: 35.9 (6) / 38.7 (3).  No shape gets under
 // ~34 us: the ring is a fixed cost of prologue (tap lists), a short dependent loop and the mirrored atomics.  Default: 64 x 128 on the 3x3
-// stride-1 layers (what was measured), the caller's tile elsewhere.  ACLGAN_HALO_TILE = 1 / 2 / 3 forces 64 x 64 / 64 x 128 / 128 x 64 on every
-// layer with Cin % 64 == 0, 4 = the caller's tile everywhere; ACLGAN_HALO_SPLIT overrides the slice count (launch_dgrad_fast).
+// stride-1 layers (what was measured), the caller's tile elsewhere.
 template <int WM, int WN, int TM, int TN>
 int launch_dgrad_halo(const ConvGeom& g, DgFP p, hipStream_t st) {
-    if (p.band == 0 && !p.ringpad && g.Ci % 64 == 0) {
-        int t = sw(SW_HALO_TILE);
-        if (t == 0 && g.k == 3 && g.s == 1 && g.Ci % 128 == 0 && WM == 2 && WN == 2 && TM == 2 && TN == 2) t = 2;
-        if (t == 1) return launch_dgrad_fast<2, 2, 1, 1>(g, p, st);       // 64 x 64
-        if (t == 2) return launch_dgrad_fast<2, 2, 1, 2>(g, p, st);       // 64 x 128
-        if (t == 3) return launch_dgrad_fast<2, 2, 2, 1>(g, p, st);       // 128 x 64
-    }
+    if (p.band == 0 && !p.ringpad && g.k == 3 && g.s == 1 && g.Ci % 128 == 0 && WM == 2 && WN == 2 && TM == 2 && TN == 2)
+        return launch_dgrad_fast<2, 2, 1, 2>(g, p, st);       // 64 x 128
     return launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
 }
 
@@ -542,10 +491,8 @@ int dgrad_fast_all(const ConvGeom& g, DgFP p, float* dxp, float* dx, int accumul
         // atomics: together = dgrad + reflection_pad2d backward
         *direct = true;
         p.dxp = dx; p.accumulate = accumulate;
-        int rc = launch_dgrad_fast_merged<WM, WN, TM, TN>(g, p, st);
-        if (rc != ACLGAN_EUNSUPPORTED) return rc;
         p.mode = 1;
-        rc = (dxp && conv_wino_ok(g)) ? conv_dgrad_wino_interior(g, p.dy, p.w, dx, accumulate, dxp, st)   // interior: Winograd (zero pad, flipped w^T)
+        int rc = (dxp && conv_wino_ok(g)) ? conv_dgrad_wino_interior(g, p.dy, p.w, dx, accumulate, dxp, st)   // interior: Winograd (zero pad, flipped w^T)
              : (dxp && conv_s2k4_wino_ok(g, 1)) ? conv_dgrad_s2k4_wino_interior(g, p.dy, p.w, dx, accumulate, dxp, st)      // 4x4 stride 2: four parity phases
                                       : launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
         if (rc) return rc;
@@ -928,7 +875,7 @@ int launch_wgrad_fast(const ConvGeom& g, WgFP p, hipStream_t st, void* det_part 
         p.dw = (float*)det_part; p.dw_zs = ndw;
         if (p.db) { p.db = (float*)det_part + (size_t)splits * ndw; p.db_zs = g.Co; }
     }
-    if (!sw(SW_NOSINGLETAP) && p.Ci % BN == 0) hipLaunchKernelGGL((conv_wgrad_fast_kernel<WM, WN, TM, TN, true>), dim3(p.nwg, ny, splits), dim3(WM * WN * 64), 0, st, p);
+    if (p.Ci % BN == 0) hipLaunchKernelGGL((conv_wgrad_fast_kernel<WM, WN, TM, TN, true>), dim3(p.nwg, ny, splits), dim3(WM * WN * 64), 0, st, p);
     else hipLaunchKernelGGL((conv_wgrad_fast_kernel<WM, WN, TM, TN, false>), dim3(p.nwg, ny, splits), dim3(WM * WN * 64), 0, st, p);
     ACL_CHECK_LAUNCH("conv_wgrad_fast_kernel");
     if (p.dw_zs) {
@@ -1020,10 +967,6 @@ int up5_wgrad_t(const ConvGeom& g, const float* x, const float* dy, float* dw, f
     return kc ? launch_wgrad_kc_any(g, p, part, st) : launch_wgrad_fast<WM, WN, TM, TN>(g, p, st);
 }
 
-// ACLGAN_UP5_BANDFOLD=1: the ring of the sub-pixel input gradient as plain stores on the padded hi-res grid + a gather over the dx pixels that
-// alias into the band, instead of fp32 atomics.  MEASURED SLOWER (round 6, profiles/r06_experiments.md): the step 82.9 against 82.3 ms (3 lanes),
-// 90.5 against 90.1 (one queue) -- the ring launch is bound by its k loop and its tail, not by the atomics; the extra launch and the 25 MB
-// round trip cost more than the atomics did.  Off; kept as a measured option (the deterministic mode uses the full-grid fold as before).
 template <int WM, int WN, int TM, int TN>
 int up5_dgrad_t(const ConvGeom& g, const float* dy, const float* w, float* dx, int accumulate, float* wp, hipStream_t st) {
     const int64_t nm = (int64_t)4 * g.Co * 9 * (g.Ci / 4);
@@ -1067,15 +1010,6 @@ int up5_dgrad_t(const ConvGeom& g, const float* dy, const float* w, float* dx, i
         if (rc) return rc;
         return conv_fold(g, dxp, dx, 1, st);
     }
-    if (sw(SW_UP5_BANDFOLD) && g.Ci % 4 == 0) {
-        // Round 6: one plain store per band position into the (otherwise untouched) padded hi-res scratch, then a gather over the dx pixels
-        // that alias into the band -- instead of 6.2 M fp32 atomics per launch (256 -> 128 layer at 256x256 B=8: 445 us for 13 GFLOP)
-        float* dxp = (float*)((char*)wp + up5_merged_bytes(g));
-        p.ringpad = 1; p.dxp = dxp; p.accumulate = 0;
-        const int rc = launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
-        if (rc) return rc;
-        return conv_fold_band(g, dxp, dx, 6, st);
-    }
     return launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
 }
 
@@ -1088,7 +1022,7 @@ size_t conv_up5_scratch_bytes(const ConvGeom& g) {
 // dgrad of a sub-pixel layer: merged phase filters, then the Winograd planes of its four phases
 size_t conv_up5_dgrad_scratch_bytes(const ConvGeom& g) {
     if (sw(SW_NOFAST) || !up5_eligible(g)) return 0;
-    const size_t padded = (sw(SW_DETERMINISTIC) || sw(SW_UP5_BANDFOLD)) ? (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float) : 0;     // ring positions on the padded hi-res grid (ordered fold / band fold)
+    const size_t padded = sw(SW_DETERMINISTIC) ? (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float) : 0;     // ring positions on the padded hi-res grid (ordered fold)
     return up5_merged_bytes(g) + std::max(conv_up5_wino_dgrad_scratch_bytes(g), padded);
 }
 // weight-gradient scratch of the tuned kernels: phase gradients of the sub-pixel layers + the partial tiles of the
@@ -1144,23 +1078,10 @@ int gemm_slices_f32(const float* A, const float* Bm, float* Cm, int T, int K, in
     p.B = 1; p.ring = 0; p.phases = 0; p.Hf = 0; p.Wf = 0;
     p.fsl = nslices; p.fsx_mod = a_mod; p.fs_x = (long long)T * K; p.fs_w = (long long)N * K; p.fs_y = (long long)T * N;
     if (N > 64) {
-        p.tiles_n = cdiv(N, 128); p.nwg = cdiv(T, 128) * p.tiles_n;
         // K is short here (the channel count): 128 x 128 tiles leave 1.5 rounds of workgroups and exposed prologues/epilogues;
         // 64 x 128 tiles at 4 workgroups per CU measured 8 % faster on the ResBlock shape (profiles/r02_experiments.md).
-        // ACLGAN_GEMM_VAR=1: 128 x 64 tiles, 3 per CU;  =2: 128 x 128 tiles, 3 per CU.
-        const int var = sw(SW_GEMM_VAR);
-        if (var == 1) {
-            p.tiles_n = cdiv(N, 64); p.nwg = cdiv(T, 128) * p.tiles_n;
-            hipLaunchKernelGGL((conv_fwd_fast_kernel<2, 2, 2, 1, 3>), dim3(p.nwg, nslices, 1), dim3(256), 0, st, p);
-        } else if (var == 2) {
-            hipLaunchKernelGGL((conv_fwd_fast_kernel<2, 2, 2, 2, 3>), dim3(p.nwg, nslices, 1), dim3(256), 0, st, p);
-        } else if (var == 3 && N % 256 == 0) {      // 64 x 256 tiles: a workgroup covers all of N = 256, V is fetched once per row tile
-            p.tiles_n = N / 256; p.nwg = cdiv(T, 64) * p.tiles_n;
-            hipLaunchKernelGGL((conv_fwd_fast_kernel<1, 4, 2, 2, 3>), dim3(p.nwg, nslices, 1), dim3(256), 0, st, p);
-        } else {
-            p.tiles_n = cdiv(N, 128); p.nwg = cdiv(T, 64) * p.tiles_n;
-            hipLaunchKernelGGL((conv_fwd_fast_kernel<2, 2, 1, 2, 4>), dim3(p.nwg, nslices, 1), dim3(256), 0, st, p);
-        }
+        p.tiles_n = cdiv(N, 128); p.nwg = cdiv(T, 64) * p.tiles_n;
+        hipLaunchKernelGGL((conv_fwd_fast_kernel<2, 2, 1, 2, 4>), dim3(p.nwg, nslices, 1), dim3(256), 0, st, p);
     } else if (N > 32) {
         p.tiles_n = cdiv(N, 64); p.nwg = cdiv(T, 256) * p.tiles_n;
         hipLaunchKernelGGL((conv_fwd_fast_kernel<4, 1, 2, 2>), dim3(p.nwg, nslices, 1), dim3(256), 0, st, p);
@@ -1200,8 +1121,6 @@ int conv_fwd_fast(const ConvGeom& g, const float* x, const float* w, const float
     p.Hi = g.Hi; p.Wi = g.Wi; p.Ci = g.Ci; p.Ho = g.Ho; p.Wo = g.Wo; p.Co = g.Co; p.k = g.k; p.s = g.s; p.p = g.p;
     p.up = g.up; p.Hu = g.Hu; p.Wu = g.Wu; p.M = g.M; p.K = g.K; p.act = g.act; p.tiles_n = 0; p.nwg = 0; p.nkz = 0;
     p.B = g.B; p.ring = 0; p.phases = 0; p.Hf = 0; p.Wf = 0;
-    // ACLGAN_BIGTILE=1: 256 x 128 tiles with 8 waves for the large layers (25 % fewer operand bytes per MFMA than 128 x 128; one workgroup per CU)
-    if (g.Co % 128 == 0 && sw(SW_BIGTILE) && g.M >= 256 * 128) return launch_fwd_fast<4, 2, 2, 2>(g, p, st);   // 256 x 128, 8 waves (experiment)
     if (g.Co > 64) return launch_fwd_fast<2, 2, 2, 2>(g, p, st);
     if (g.Co > 32) return launch_fwd_fast<4, 1, 2, 2>(g, p, st);
     return launch_fwd_fast<4, 1, 2, 1>(g, p, st);
@@ -1220,7 +1139,6 @@ int conv_dgrad_fast(const ConvGeom& g, const float* dy, const float* w, float* d
     p.Hc = cdiv(g.Hp, g.s); p.Wc = cdiv(g.Wp, g.s); p.Mc = 0; p.tiles_n = 0; p.nwg = 0; p.ksplit = 1;
     p.mode = 0; p.accumulate = 0; p.pad = g.p; p.B = g.B; p.Hi = g.Hu; p.Wi = g.Wu;
     p.dyv = 0; p.py = 0; p.px = 0; p.Hf = 0; p.Wf = 0; p.band = 0; p.upshift = 0; p.Hd = g.Hu; p.Wd = g.Wu;
-    if (g.Ci % 128 == 0 && sw(SW_BIGTILE) && g.M >= 256 * 128) return dgrad_fast_all<4, 2, 2, 2>(g, p, dxp, dx, accumulate, direct, st);
     if (g.Ci > 64) return dgrad_fast_all<2, 2, 2, 2>(g, p, dxp, dx, accumulate, direct, st);
     if (g.Ci > 32) return dgrad_fast_all<4, 1, 2, 2>(g, p, dxp, dx, accumulate, direct, st);
     return dgrad_fast_all<4, 1, 2, 1>(g, p, dxp, dx, accumulate, direct, st);
@@ -1312,9 +1230,8 @@ double conv_exec_flops(const ConvGeom& g, int which, bool f16) {
         if (wgrad_kc_ok(g) && conv_wgrad_wino_scratch_bytes(g)) return pipe_flops(g.B, g.Hi, g.Wi, g.Ci, g.Co, 1);
         return direct;
     }
-    // (the input gradient's phases run only where dgrad_fast_all writes the interior straight into dx: not under ACLGAN_NODIRECT, and not
-    //  when the opt-in merged interior + halo launch (ACLGAN_MERGEDHALO) takes the layer first)
-    const bool s2k4_dg_direct = !sw(SW_NODIRECT) && !sw(SW_MERGEDHALO);
+    // (the input gradient's phases run only where dgrad_fast_all writes the interior straight into dx: not under ACLGAN_NODIRECT)
+    const bool s2k4_dg_direct = !sw(SW_NODIRECT);
     if (!f16 && !sw(SW_NOFAST) && which < 2 && conv_s2k4_wino_ok(g, which) && (which == 0 || s2k4_dg_direct)) {
         if (which == 0) return fused_flops(g.B, g.Ho, g.Wo, g.Ci, g.Co, 1, 4);
         const double halo = 2.0 * g.B * ((double)g.Hp * g.Wp - (double)g.Hi * g.Wi) * g.Ci * g.Co * 2.0;      // 2 of the 4 taps of a parity class per ring position

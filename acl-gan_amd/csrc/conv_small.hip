@@ -259,91 +259,6 @@ __global__ void __launch_bounds__(256) conv_thin_out_kernel(const float* __restr
     }
 }
 
-// ---------------- thin (CS = 3 or 4 channels) -> 64 channels, 7x7 / stride 1 / reflect pad 3, on v_mfma_f32_32x32x2 ----------------
-// The forward of CE0 / SE0 (networks.py:216,234).  (The same scheme was tried for the dgrad of the 64 -> 4 layer, K = 196 onto
-// the padded grid: 0.28 ms against 0.24 ms for the general kernel + fold -- not kept.)
-// GEMM per 8x32-pixel tile: M = 256 pixels (wave = 2 image rows = 2 M-tiles), N = 64, K = 49*CS (147 / 196).  With so few
-// input channels an im2col tile would be all index math; instead the (reflect / zero padded) input patch sits in LDS
-// once and every A fragment is a ds_read_b32 at  pixel_base + const(k): k = (tap, c) -> patch offset k + ky*(PW-7)*CS,
-// a compile-time immediate (the K loop is fully unrolled); the two lane halves (k, k+1) differ by 1 float except where
-// k+1 starts a new filter row, handled by a second per-lane base.  Weights: LDS [k][64+1].
-// __launch_bounds__ second argument = min waves per SIMD (what LDS allows): caps the VGPRs the fully unrolled K loop may take
-template <int CS>
-__global__ void __launch_bounds__(256, CS == 3 ? 3 : 2) conv_thin_in_kernel(const float* __restrict__ in, const float* __restrict__ w,
-                                                           const float* __restrict__ bias, float* __restrict__ out,
-                                                           int H, int W, int act, int tiles_x, int tiles_y) {
-    constexpr int K = 7, P = 3, PH = TH + K - 1, PW = TW + K - 1;
-    constexpr int KT = K * K * CS, KS = (KT + 1) / 2, LDW = 65, ROWJ = (PW - K) * CS;   // ROWJ: extra patch offset per filter row
-    __shared__ float patch[(PH + 1) * PW * CS];          // + one zero row: the odd-K pad element reads it
-    __shared__ float wl[2 * KS * LDW];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, kh = lane >> 5;
-    const int Ho = H, Wo = W;
-    // weights -> LDS [k][co], zero row for the K pad
-    for (int i = tid; i < 2 * KS * 64; i += 256) {
-        const int co = i / (2 * KS), k = i - co * (2 * KS);          // consecutive threads walk k: coalesced along OHWI's (tap, c)
-        wl[k * LDW + co] = k < KT ? w[(size_t)co * KT + k] : 0.f;
-    }
-    for (int tt = 0; tt < 2; ++tt) {                                 // two vertically adjacent tiles per workgroup (weights staged once)
-        const int tyi = (blockIdx.x % ((tiles_y + 1) / 2)) * 2 + tt;
-        const int rest = blockIdx.x / ((tiles_y + 1) / 2);
-        const int txi = rest % tiles_x, b = rest / tiles_x;
-        if (tyi >= tiles_y) break;                                   // block-uniform
-        const int ty0 = tyi * TH, tx0 = txi * TW;
-        __syncthreads();
-        for (int i = tid; i < (PH + 1) * PW * CS; i += 256) {
-            const int pix = i / CS, c = i - pix * CS;
-            const int py = pix / PW, px = pix - py * PW;
-            const int gy = ty0 + py - P, gx = tx0 + px - P;
-            float v = 0.f;
-            if (py < PH) {
-                // clamp after reflecting: halo pixels of tiles that overhang the image feed only outputs that are never stored
-                const int iy = min(max(refl(gy, H), 0), H - 1), ix = min(max(refl(gx, W), 0), W - 1);
-                v = in[((size_t)(b * H + iy) * W + ix) * CS + c];
-            }
-            patch[i] = v;
-        }
-        __syncthreads();
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        const float* pN = patch + ((2 * wave) * PW + l31) * CS + kh;              // lane half kh reads k+kh: +1 float ...
-        const float* pX = patch + ((2 * wave) * PW + l31) * CS + kh * (1 + ROWJ);  // ... or +1 plus the row jump when k+1 opens a filter row
-        const float* pb = wl + kh * LDW + l31;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int k0 = 2 * s;
-            const int off0 = k0 + (k0 / (K * CS)) * ROWJ;                        // compile-time after unrolling
-            const bool jump = ((k0 + 1) % (K * CS)) == 0;
-            const float* pa = jump ? pX : pN;
-            const float a0 = pa[off0], a1 = pa[off0 + PW * CS];
-            const float b0 = pb[k0 * LDW], b1 = pb[k0 * LDW + 32];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int co = l31 + 32 * j;
-            const float bv = bias ? bias[co] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int oy = ty0 + 2 * wave + i;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ox = tx0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                    if (oy < Ho && ox < Wo) out[((size_t)(b * Ho + oy) * Wo + ox) * 64 + co] = act_apply(acc[i][j][r] + bv, act);
-                }
-            }
-        }
-    }
-}
-
 // ---------------- wgrad with one THIN side (<= 4 channels) and one 64-channel side, 7x7 / stride 1 / pad 3 ----------------
 //   WIDE_X = true : Cin = 64, Cout = 4   (DO, networks.py:260): wide = x gathered at the tap-shifted position, thin = dy
 //   WIDE_X = false: Cout = 64, Cin <= 4  (CE0 / SE0, networks.py:216,234): wide = dy, thin = x at the tap-shifted position
@@ -596,9 +511,10 @@ __global__ void __launch_bounds__(256) conv_s2k4_thin_dgrad_kernel(const float* 
 }
 
 // ---------------- round 6: thin (CS = 3 / 4 / 6 channels) -> 64 channels, K x K / stride S / reflect pad P, pipelined ----------------
-// conv_thin_in_kernel's GEMM scheme (patch in LDS, every A fragment a ds_read_b32 at pixel_base + const(k)) generalised to the first
-// discriminator layers (4x4 stride 2 pad 1, Cin 3 / 6: networks.py:41 -- they ran on the general implicit-GEMM kernel with scalar gathers,
-// 59 - 87 us for 67 MB of output) and restructured around what the PMC pass of the 7x7 kernel showed (profiles/r06_experiments.md section 5:
+// The forward of CE0 / SE0 (7x7 stride 1 pad 3, Cin 3 / 4: networks.py:216,234) and of the first discriminator layers (4x4 stride 2 pad 1,
+// Cin 3 / 6: networks.py:41).  GEMM per 8x32-pixel tile on v_mfma_f32_32x32x2: M = 256 pixels, N = 64, K = K*K*CS.  With so few input
+// channels an im2col tile would be all index math; instead the (reflect padded) input patch sits in LDS and every A fragment is a
+// ds_read_b32 at pixel_base + const(k).  Built around what the PMC pass of the round-5 7x7 kernel showed (profiles/r06_experiments.md section 5:
 // MFMA pipe 45 % busy, 4.5 VALU instructions per MFMA of which 4 in the staging loops and the store epilogue, waves parked 42 % of the time --
 // every workgroup of a CU in its load phase at once):
 //   * a workgroup walks `tpw` vertically adjacent tiles with the weights staged ONCE, and fetches the patch of tile t + 1 into registers
@@ -709,7 +625,7 @@ static int launch_thin_in2(const ConvGeom& g, const float* x, const float* w, co
 }
 int conv_fwd_small(const ConvGeom& g, const float* x, const float* w, const float* bias, float* y, hipStream_t st) {
     // round 6: the first discriminator layers (4x4 stride 2 reflect pad 1, Cin 3 / 6 -> 64: networks.py:41)
-    if (!sw(SW_NOSMALL) && !sw(SW_NOTHIN) && sw(SW_THININ2) && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && g.Co == 64 && (g.Ci == 3 || g.Ci == 6) &&
+    if (!sw(SW_NOSMALL) && !sw(SW_NOTHIN) && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && g.Co == 64 && (g.Ci == 3 || g.Ci == 6) &&
         g.Hi >= 2 && g.Wi >= 2)
         return g.Ci == 3 ? launch_thin_in2<3, 4, 2, 1>(g, x, w, bias, y, st) : launch_thin_in2<6, 4, 2, 1>(g, x, w, bias, y, st);
     if (sw(SW_NOSMALL) || g.s != 1 || g.up || g.k != 7 || g.p != 3 || g.Hu < g.k || g.Wu < g.k) return ACLGAN_EUNSUPPORTED;
@@ -719,16 +635,8 @@ int conv_fwd_small(const ConvGeom& g, const float* x, const float* w, const floa
         ACL_CHECK_LAUNCH("conv_thin_out_kernel<fwd>");
         return ACLGAN_OK;
     }
-    if (!sw(SW_NOTHIN) && sw(SW_THININ2) && g.Co == 64 && (g.Ci == 3 || g.Ci == 4))
+    if (!sw(SW_NOTHIN) && g.Co == 64 && (g.Ci == 3 || g.Ci == 4))
         return g.Ci == 3 ? launch_thin_in2<3, 7, 1, 3>(g, x, w, bias, y, st) : launch_thin_in2<4, 7, 1, 3>(g, x, w, bias, y, st);
-    if (!sw(SW_NOTHIN) && g.Co == 64 && (g.Ci == 3 || g.Ci == 4)) {
-        const int tx = cdiv(g.Wi, TW), ty = cdiv(g.Hi, TH);
-        const dim3 grid(g.B * tx * ((ty + 1) / 2));
-        if (g.Ci == 3) hipLaunchKernelGGL((conv_thin_in_kernel<3>), grid, dim3(256), 0, st, x, w, bias, y, g.Hi, g.Wi, g.act, tx, ty);
-        else hipLaunchKernelGGL((conv_thin_in_kernel<4>), grid, dim3(256), 0, st, x, w, bias, y, g.Hi, g.Wi, g.act, tx, ty);
-        ACL_CHECK_LAUNCH("conv_thin_in_kernel<fwd>");
-        return ACLGAN_OK;
-    }
     if (g.Co != 4 || g.Ci % 16 != 0) return ACLGAN_EUNSUPPORTED;
     const int tx = cdiv(g.Wi, TW), ty = cdiv(g.Hi, TH);
     hipLaunchKernelGGL(conv_fwd_co4_kernel<7>, dim3(g.B * tx * ty), dim3(256), 0, st, x, w, bias, y, g.Hi, g.Wi, g.Ci, g.act, tx, ty);
@@ -739,7 +647,7 @@ int conv_fwd_small(const ConvGeom& g, const float* x, const float* w, const floa
 // dgrad of a thin-input 7x7 layer onto the padded grid dxp [B][H+6][W+6][Ci] (the caller folds the reflection)
 // the first discriminator layers (4x4 stride 2 pad 1, Cin 3 / 6): input gradient on the VALU kernel below (also conv_exec_flops' predicate)
 bool conv_s2k4_thin_dgrad_ok(const ConvGeom& g) {
-    return !sw(SW_NOSMALL) && !sw(SW_NOTHIN) && sw(SW_THININ2) && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && (g.Ci == 3 || g.Ci == 6) && g.Co % 4 == 0 &&
+    return !sw(SW_NOSMALL) && !sw(SW_NOTHIN) && !g.up && g.k == 4 && g.s == 2 && g.p == 1 && (g.Ci == 3 || g.Ci == 6) && g.Co % 4 == 0 &&
            g.Hi % 2 == 0 && g.Wi % 2 == 0;
 }
 int conv_dgrad_small(const ConvGeom& g, const float* dy, const float* w, float* dxp, hipStream_t st) {

@@ -131,14 +131,7 @@ struct StreamPool {
         static std::mutex mu;
         std::lock_guard<std::mutex> lock(mu);
         if (!s[i]) {
-            hipError_t e = hipSuccess;
-            const int prio = sw(SW_SIDE_PRIO);      // ACLGAN_SIDE_PRIO=1: the parameter-gradient stream at the highest priority the device offers (measured neutral, round 4)
-            // ACLGAN_LANE_PRIO=-1: lanes 1.. at the LOWEST priority (lane 0, the caller's stream, carries the chain everything waits for)
-            const int lprio = sw(SW_LANE_PRIO);
-            int lo = 0, hi = 0;
-            if (i == 0 && prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) e = hipStreamCreateWithPriority(&s[i], hipStreamNonBlocking, prio > 0 ? hi : lo);
-            else if (i > 0 && lprio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) e = hipStreamCreateWithPriority(&s[i], hipStreamNonBlocking, lprio > 0 ? hi : lo);
-            else e = hipStreamCreateWithFlags(&s[i], hipStreamNonBlocking);
+            const hipError_t e = hipStreamCreateWithFlags(&s[i], hipStreamNonBlocking);
             if (e != hipSuccess) { s[i] = nullptr; return hip_fail(e, "stream pool"); }
         }
         *out = s[i];
@@ -359,17 +352,14 @@ struct aclgan_ctx {
             if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) capturing = true;
             else (void)hipGetLastError();
         }
-        // ACLGAN_CAPTURE_LANES=1 (investigation switch, round 6): capture the pooled lanes as they are
-        const int cap_lanes = sw(SW_CAPTURE_LANES);
-        const bool cap_one = capturing && !cap_lanes;
-        if (cap_one) nlanes = 1;
+        if (capturing) nlanes = 1;
         cur_lane = 0; st0 = st;
         for (int l = 0; l < MAXL; ++l) { lane_evs[l].clear(); hw[l] = 0; lane_dirty[l] = false; for (int m = 0; m < MAXL; ++m) seen[l][m] = 0; }
         ev_next = 0;
         if (dry) return ACLGAN_OK;
         // (parameter-gradient stream first, then the lanes: with the caller's stream that is one hardware queue each up to 3 lanes)
         if (sw(SW_SIDE_STREAM) && !st2_pool) { int rc = aclgan::StreamPool::of_device().get(0, &st2_pool); if (rc) return rc; }
-        st2 = cap_one ? st : st2_pool;
+        st2 = capturing ? st : st2_pool;
         for (int l = 1; l < nlanes; ++l)
             if (!lane_st[l]) { int rc = aclgan::StreamPool::of_device().get(l, &lane_st[l]); if (rc) return rc; }
         return ACLGAN_OK;
@@ -963,8 +953,7 @@ static int prefill_wino_u(aclgan_ctx& c, int net, int B, int H, int W, bool trai
 // previous call's optimizer step wrote the parameters on the caller's stream.
 static int prefill_on_side_lane(aclgan_ctx& c, int B, int H, int W, bool train) {
     const int AB = ACLGAN_NET_GEN_AB, BA = ACLGAN_NET_GEN_BA;
-    const int on_lane = sw(SW_PREFILL_LANE);      // ACLGAN_PREFILL_LANE=0: back in lane 0's preamble (A/B switch)
-    if (c.nlanes <= 1 || !on_lane) { CHK(prefill_wino_u(c, AB, B, H, W, train)); return prefill_wino_u(c, BA, B, H, W, train); }
+    if (c.nlanes <= 1) { CHK(prefill_wino_u(c, AB, B, H, W, train)); return prefill_wino_u(c, BA, B, H, W, train); }
     const int LP = c.nlanes - 1;
     CHK(c.mark());
     const int k0 = c.nck(0) - 1;

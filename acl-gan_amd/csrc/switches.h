@@ -13,14 +13,12 @@ enum SwitchId {
     // environment only
     SW_DETERMINISTIC,
     SW_NOFAST, SW_NOUP5, SW_SPLIT_NWG,
-    SW_MERGEDHALO, SW_HALO_TILE, SW_HALO_SPLIT, SW_BIGTILE, SW_NOWGKC, SW_NOSINGLETAP, SW_UP5_BANDFOLD, SW_NOUP5DGRAD, SW_GEMM_VAR,
+    SW_NOWGKC, SW_NOUP5DGRAD,
     SW_NOSTATFUSE, SW_NOKEEPV, SW_NODIRECT,
-    SW_TILE16,
-    SW_GLDS_SPEC, SW_GLDS_NBUF, SW_NOWGRAD16S, SW_WGRAD16S_MINPIX, SW_NOGLDS16,
-    SW_NOSMALL, SW_NOTHIN, SW_THININ2,
+    SW_NOWGRAD16S, SW_WGRAD16S_MINPIX, SW_NOGLDS16,
+    SW_NOSMALL, SW_NOTHIN,
     SW_NOWINO, SW_NOWINOUP5, SW_WINO_VEC, SW_WINO_VEC3,
-    SW_ROCTX, SW_SIDE_PRIO, SW_LANE_PRIO, SW_NOUCACHE, SW_ACT16, SW_CO16, SW_SIDE_STREAM, SW_CAPTURE_LANES, SW_KEEPV_BUDGET_GB,
-    SW_PREFILL_LANE,
+    SW_ROCTX, SW_NOUCACHE, SW_ACT16, SW_CO16, SW_SIDE_STREAM, SW_KEEPV_BUDGET_GB,
     SW_COUNT
 };
 

@@ -34,7 +34,6 @@ struct Switch {
     double (*parse)(const char*);     // variables that are not an integer: the value is this function of the text
 };
 
-double parse_tile16(const char* s) { return s[0] == 'w' ? 1.0 : 0.0; }
 double parse_real(const char* s) { return atof(s); }
 const int VEC_124 = (1 << 1) | (1 << 2) | (1 << 4);
 
@@ -58,41 +57,26 @@ const Switch kSwitches[SW_COUNT] = {
     {"nofast",            "ACLGAN_NOFAST",            0,  R_BOOL,  0, 0,       0, nullptr},
     {"noup5",             "ACLGAN_NOUP5",             0,  R_BOOL,  0, 0,       0, nullptr},
     {"split_nwg",         "ACLGAN_SPLIT_NWG",         256, R_INT,  0, 0,       0, nullptr},
-    {"mergedhalo",        "ACLGAN_MERGEDHALO",        0,  R_BOOL,  0, 0,       0, nullptr},
-    {"halo_tile",         "ACLGAN_HALO_TILE",         0,  R_RANGE, 0, 4,       0, nullptr},
-    {"halo_split",        "ACLGAN_HALO_SPLIT",        0,  R_INT,   0, 0,       0, nullptr},
-    {"bigtile",           "ACLGAN_BIGTILE",           0,  R_BOOL,  0, 0,       0, nullptr},
     {"nowgkc",            "ACLGAN_NOWGKC",            0,  R_BOOL,  0, 0,       0, nullptr},
-    {"nosingletap",       "ACLGAN_NOSINGLETAP",       0,  R_BOOL,  0, 0,       0, nullptr},
-    {"up5_bandfold",      "ACLGAN_UP5_BANDFOLD",      0,  R_BOOL,  0, 0,       0, nullptr},
     {"noup5dgrad",        "ACLGAN_NOUP5DGRAD",        0,  R_BOOL,  0, 0,       0, nullptr},
-    {"gemm_var",          "ACLGAN_GEMM_VAR",          0,  R_INT,   0, 0,       0, nullptr},
     {"nostatfuse",        "ACLGAN_NOSTATFUSE",        0,  R_BOOL,  0, 0,       0, nullptr},
     {"nokeepv",           "ACLGAN_NOKEEPV",           0,  R_BOOL,  0, 0,       0, nullptr},
     {"nodirect",          "ACLGAN_NODIRECT",          0,  R_BOOL,  0, 0,       0, nullptr},
-    {"tile16",            "ACLGAN_TILE16",            0,  R_INT,   0, 0,       0, parse_tile16},
-    {"glds_spec",         "ACLGAN_GLDS_SPEC",         0,  R_INT,   0, 0,       0, nullptr},
-    {"glds_nbuf",         "ACLGAN_GLDS_NBUF",         0,  R_INT,   0, 0,       0, nullptr},
     {"nowgrad16s",        "ACLGAN_NOWGRAD16S",        0,  R_BOOL,  0, 0,       0, nullptr},
     {"wgrad16s_minpix",   "ACLGAN_WGRAD16S_MINPIX",   64, R_INT,   0, 0,       0, nullptr},
     {"noglds16",          "ACLGAN_NOGLDS16",          0,  R_BOOL,  0, 0,       0, nullptr},
     {"nosmall",           "ACLGAN_NOSMALL",           0,  R_BOOL,  0, 0,       0, nullptr},
     {"nothin",            "ACLGAN_NOTHIN",            0,  R_BOOL,  0, 0,       0, nullptr},
-    {"thinin2",           "ACLGAN_THININ2",           1,  R_BOOL,  0, 0,       0, nullptr},
     {"nowino",            "ACLGAN_NOWINO",            0,  R_BOOL,  0, 0,       0, nullptr},
     {"nowinoup5",         "ACLGAN_NOWINOUP5",         0,  R_BOOL,  0, 0,       0, nullptr},
     {"wino_vec",          "ACLGAN_WINO_VEC",          2,  R_ONEOF, VEC_124, 0, 0, nullptr},
     {"wino_vec3",         "ACLGAN_WINO_VEC3",         2,  R_ONEOF, VEC_124, 0, 0, nullptr},
     {"roctx",             "ACLGAN_ROCTX",             0,  R_BOOL,  0, 0,       0, nullptr},
-    {"side_prio",         "ACLGAN_SIDE_PRIO",         0,  R_INT,   0, 0,       0, nullptr},
-    {"lane_prio",         "ACLGAN_LANE_PRIO",         0,  R_INT,   0, 0,       0, nullptr},
     {"noucache",          "ACLGAN_NOUCACHE",          0,  R_BOOL,  0, 0,       0, nullptr},
     {"act16",             "ACLGAN_ACT16",             1,  R_BOOL,  0, 0,       0, nullptr},
     {"co16",              "ACLGAN_CO16",              1,  R_BOOL,  0, 0,       0, nullptr},
     {"side_stream",       "ACLGAN_SIDE_STREAM",       1,  R_BOOL,  0, 0,       0, nullptr},
-    {"capture_lanes",     "ACLGAN_CAPTURE_LANES",     0,  R_BOOL,  0, 0,       0, nullptr},
     {"keepv_budget_gb",   "ACLGAN_KEEPV_BUDGET_GB",   64, R_INT,   0, 0,       0, parse_real},
-    {"prefill_lane",      "ACLGAN_PREFILL_LANE",      1,  R_BOOL,  0, 0,       0, nullptr},
 };
 
 int normalise(const Switch& s, int v, bool from_env) {

@@ -128,8 +128,8 @@ if has split; then      # round 6, review item 4: the split-bf16 (6 products) in
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-value -Iscripts/microbench -o /tmp/split_bf16_loop scripts/microbench/split_bf16_loop.hip > $O/split_build.log 2>&1
     timeout 300 /tmp/split_bf16_loop > $O/microbench_split_bf16_loop.txt 2>&1; cat $O/microbench_split_bf16_loop.txt | tee -a $O/progress.log
 fi
-if has thin; then      # round 6: the image-side layers in isolation, new kernels against ACLGAN_THININ2=0
-    (timeout 300 python scripts/probe_thin.py 10 2>&1 | grep -v amdgpu) > $O/probe_thin.txt; (ACLGAN_THININ2=0 timeout 300 python scripts/probe_thin.py 10 2>&1 | grep -v amdgpu) > $O/probe_thin_round5_kernels.txt
+if has thin; then      # round 6: the image-side layers in isolation
+    (timeout 300 python scripts/probe_thin.py 10 2>&1 | grep -v amdgpu) > $O/probe_thin.txt
     paste -d'|' $O/probe_thin.txt $O/probe_thin_round5_kernels.txt | cut -c 1-200 | tee -a $O/progress.log
 fi
 if has s2k4; then (timeout 300 python scripts/bench_s2k4.py 2>&1 | grep -v amdgpu) > $O/s2k4_direct_vs_fused_per_shape.txt; cat $O/s2k4_direct_vs_fused_per_shape.txt | tee -a $O/progress.log; fi

@@ -20,7 +20,5 @@ B16="python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-other-configs -
 timeout 300 $B16 --lanes 1 > $OUT/bench_bf16_lanes1.json 2>/dev/null; summ $OUT/bench_bf16_lanes1.json
 timeout 300 $B16 --lanes 3 > $OUT/bench_bf16_lanes3.json 2>/dev/null; summ $OUT/bench_bf16_lanes3.json
 ACLGAN_GLDS_TILE=4 timeout 300 $B16 --lanes 3 > $OUT/bench_bf16_tile4.json 2>/dev/null; summ $OUT/bench_bf16_tile4.json
-ACLGAN_GLDS_TILE=2 ACLGAN_GLDS_SPEC=1 timeout 300 $B16 --lanes 3 > $OUT/bench_bf16_tile2_spec.json 2>/dev/null; summ $OUT/bench_bf16_tile2_spec.json
-ACLGAN_GLDS_SPEC=1 timeout 300 $B16 --lanes 3 > $OUT/bench_bf16_spec.json 2>/dev/null; summ $OUT/bench_bf16_spec.json
 timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-other-configs --no-launch-floor --dtype fp16 --lanes 3 > $OUT/bench_fp16_b32.json 2>/dev/null; summ $OUT/bench_fp16_b32.json
 tail -25 $OUT/tests.log

@@ -13,8 +13,6 @@ PY
 }
 F="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs"
 timeout 400 $F > $OUT/floor_default.json 2>/dev/null; summ $OUT/floor_default.json
-ACLGAN_PREFILL_LANE=0 timeout 400 $F > $OUT/floor_prefill_lane0.json 2>/dev/null; summ $OUT/floor_prefill_lane0.json
-ACLGAN_THININ2=0 timeout 400 $F > $OUT/floor_thinin2_off.json 2>/dev/null; summ $OUT/floor_thinin2_off.json
 ACLGAN_NOWINOS2=1 timeout 400 $F > $OUT/floor_s2k4_off.json 2>/dev/null; summ $OUT/floor_s2k4_off.json
 B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs --no-launch-floor"
 for warm in 1 0; do for ps in 1 2; do for ln in 2 3; do

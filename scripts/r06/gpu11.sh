@@ -23,6 +23,5 @@ for dt in bf16 fp16; do
   run act16_0 ACLGAN_ACT16=0
   run nostatfuse ACLGAN_NOSTATFUSE=1
   run lanes2 ACLGAN_LANES=2
-  run prefill0 ACLGAN_PREFILL_LANE=0
   run default2 A=1
 done

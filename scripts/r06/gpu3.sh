@@ -15,8 +15,6 @@ except Exception as e: print(sys.argv[1], "ERR", e)
 PY
 }
 timeout 300 $B > $OUT/bench_default.json 2>$OUT/bench_default.err; summ $OUT/bench_default.json
-ACLGAN_UP5_BANDFOLD=0 timeout 300 $B > $OUT/bench_nobandfold.json 2>/dev/null; summ $OUT/bench_nobandfold.json
 timeout 300 $B > $OUT/bench_default2.json 2>/dev/null; summ $OUT/bench_default2.json
 timeout 300 $B --lanes 1 > $OUT/bench_lanes1.json 2>/dev/null; summ $OUT/bench_lanes1.json
-ACLGAN_UP5_BANDFOLD=0 timeout 300 $B --lanes 1 > $OUT/bench_lanes1_nobandfold.json 2>/dev/null; summ $OUT/bench_lanes1_nobandfold.json
 (timeout 900 python -m pytest tests/test_gpu_fullsize.py -m gpu -q -s -k "256_b8" 2>&1 | grep -E "worst|passed|failed|rel errors" | cut -c 1-700) | tee $OUT/pytest_fullsize_256.log

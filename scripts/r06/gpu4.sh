@@ -14,12 +14,9 @@ except Exception as e: print(sys.argv[1], "ERR", e)
 PY
 }
 timeout 300 $B > $OUT/bench_default.json 2>$OUT/bench_default.err; summ $OUT/bench_default.json
-ACLGAN_UP5_BANDFOLD=0 timeout 300 $B > $OUT/bench_nobandfold.json 2>/dev/null; summ $OUT/bench_nobandfold.json
 timeout 300 $B --lanes 1 > $OUT/bench_lanes1.json 2>/dev/null; summ $OUT/bench_lanes1.json
-ACLGAN_UP5_BANDFOLD=0 timeout 300 $B --lanes 1 > $OUT/bench_lanes1_nobandfold.json 2>/dev/null; summ $OUT/bench_lanes1_nobandfold.json
 timeout 300 $B --dtype bf16 > $OUT/bench_bf16.json 2>/dev/null; summ $OUT/bench_bf16.json
 rm -rf /tmp/prof_t; ACLGAN_SIDE_STREAM=0 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_t -o p -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-launch-floor --no-other-configs > $OUT/prof.log 2>&1
 DB=$(find /tmp/prof_t -name "*.db" | head -1); python scripts/rocpd_bygrid.py $DB 6 "" 100000 > $OUT/by_grid_ss0.txt 2>&1; python scripts/rocpd_stats.py $DB > $OUT/kernel_stats_ss0.txt 2>&1; grep -E "dgrad_fast|fold_band" $OUT/by_grid_ss0.txt | head -12; tail -1 $OUT/kernel_stats_ss0.txt
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -o /tmp/capture_lanes scripts/debug/capture_lanes.hip > $OUT/capture_build.log 2>&1
 timeout 300 /tmp/capture_lanes > $OUT/capture_lanes.txt 2>&1; cat $OUT/capture_lanes.txt
-(ACLGAN_CAPTURE_LANES=1 timeout 600 python -m pytest tests/test_gpu_graph.py -m gpu -q -x -k "fp32" 2>&1 | tail -25) > $OUT/graph_with_lanes.log; tail -12 $OUT/graph_with_lanes.log | cut -c 1-400

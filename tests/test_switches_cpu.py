@@ -19,21 +19,19 @@ SWITCHES = {
     "wino_fused": ("ACLGAN_WINO_FUSED", 1), "wino_wgrad_fused": ("ACLGAN_WINO_WGRAD_FUSED", 1), "wino_s2k4": ("ACLGAN_NOWINOS2", 1),
     "dgrad16s_direct": ("ACLGAN_DGRAD16S_DIRECT", 0), "fwd16_patch": ("ACLGAN_FWD16_PATCH", 1),
     "deterministic": ("ACLGAN_DETERMINISTIC", 0), "nofast": ("ACLGAN_NOFAST", 0), "noup5": ("ACLGAN_NOUP5", 0),
-    "split_nwg": ("ACLGAN_SPLIT_NWG", 256), "mergedhalo": ("ACLGAN_MERGEDHALO", 0), "halo_tile": ("ACLGAN_HALO_TILE", 0),
-    "halo_split": ("ACLGAN_HALO_SPLIT", 0), "bigtile": ("ACLGAN_BIGTILE", 0), "nowgkc": ("ACLGAN_NOWGKC", 0),
-    "nosingletap": ("ACLGAN_NOSINGLETAP", 0), "up5_bandfold": ("ACLGAN_UP5_BANDFOLD", 0), "noup5dgrad": ("ACLGAN_NOUP5DGRAD", 0),
-    "gemm_var": ("ACLGAN_GEMM_VAR", 0), "nostatfuse": ("ACLGAN_NOSTATFUSE", 0), "nokeepv": ("ACLGAN_NOKEEPV", 0),
-    "nodirect": ("ACLGAN_NODIRECT", 0), "tile16": ("ACLGAN_TILE16", 0), "glds_spec": ("ACLGAN_GLDS_SPEC", 0),
-    "glds_nbuf": ("ACLGAN_GLDS_NBUF", 0), "nowgrad16s": ("ACLGAN_NOWGRAD16S", 0), "wgrad16s_minpix": ("ACLGAN_WGRAD16S_MINPIX", 64),
-    "noglds16": ("ACLGAN_NOGLDS16", 0), "nosmall": ("ACLGAN_NOSMALL", 0), "nothin": ("ACLGAN_NOTHIN", 0), "thinin2": ("ACLGAN_THININ2", 1),
+    "split_nwg": ("ACLGAN_SPLIT_NWG", 256), "nowgkc": ("ACLGAN_NOWGKC", 0), "noup5dgrad": ("ACLGAN_NOUP5DGRAD", 0),
+    "nostatfuse": ("ACLGAN_NOSTATFUSE", 0), "nokeepv": ("ACLGAN_NOKEEPV", 0), "nodirect": ("ACLGAN_NODIRECT", 0),
+    "nowgrad16s": ("ACLGAN_NOWGRAD16S", 0), "wgrad16s_minpix": ("ACLGAN_WGRAD16S_MINPIX", 64),
+    "noglds16": ("ACLGAN_NOGLDS16", 0), "nosmall": ("ACLGAN_NOSMALL", 0), "nothin": ("ACLGAN_NOTHIN", 0),
     "nowino": ("ACLGAN_NOWINO", 0), "nowinoup5": ("ACLGAN_NOWINOUP5", 0), "wino_vec": ("ACLGAN_WINO_VEC", 2),
-    "wino_vec3": ("ACLGAN_WINO_VEC3", 2), "roctx": ("ACLGAN_ROCTX", 0), "side_prio": ("ACLGAN_SIDE_PRIO", 0),
-    "lane_prio": ("ACLGAN_LANE_PRIO", 0), "noucache": ("ACLGAN_NOUCACHE", 0), "act16": ("ACLGAN_ACT16", 1), "co16": ("ACLGAN_CO16", 1),
-    "side_stream": ("ACLGAN_SIDE_STREAM", 1), "capture_lanes": ("ACLGAN_CAPTURE_LANES", 0),
-    "keepv_budget_gb": ("ACLGAN_KEEPV_BUDGET_GB", 64), "prefill_lane": ("ACLGAN_PREFILL_LANE", 1),
+    "wino_vec3": ("ACLGAN_WINO_VEC3", 2), "roctx": ("ACLGAN_ROCTX", 0), "noucache": ("ACLGAN_NOUCACHE", 0), "act16": ("ACLGAN_ACT16", 1),
+    "co16": ("ACLGAN_CO16", 1), "side_stream": ("ACLGAN_SIDE_STREAM", 1), "keepv_budget_gb": ("ACLGAN_KEEPV_BUDGET_GB", 64),
 }
 SETTABLE = ["lanes", "u_batch", "norm_mask", "mlp_fused", "fault_at", "glds_tile", "wino_x3", "wino_fused", "wino_wgrad_fused", "wino_s2k4",
             "dgrad16s_direct", "fwd16_patch"]
+# retired experiments: no longer keys of the library
+RETIRED = ["mergedhalo", "up5_bandfold", "gemm_var", "glds_spec", "glds_nbuf", "bigtile", "tile16", "halo_tile", "halo_split", "side_prio",
+           "lane_prio", "capture_lanes", "nosingletap", "thinin2", "prefill_lane"]
 
 _BOOL = [("1", 1), ("3", 1), ("0", 0), ("", 0)]              # nonzero -> 1 (atoi: "" is 0)
 _ON_UNLESS_0 = [("0", 0), ("", 0), ("2", 1)]                 # default 1, off when the variable reads as 0
@@ -48,23 +46,15 @@ PARSE = {
     "wino_s2k4": [("1", 0), ("5", 0), ("0", 1)],
     "dgrad16s_direct": _BOOL, "deterministic": _BOOL, "nofast": _BOOL, "noup5": _BOOL,
     "split_nwg": [("128", 128), ("", 0)],
-    "mergedhalo": _BOOL,
-    "halo_tile": [("1", 1), ("4", 4), ("5", 0), ("-1", 0)],
-    "halo_split": [("3", 3), ("-1", -1)],
-    "bigtile": _BOOL, "nowgkc": _BOOL, "nosingletap": _BOOL, "up5_bandfold": _BOOL, "noup5dgrad": _BOOL,
-    "gemm_var": [("1", 1), ("2", 2)],
+    "nowgkc": _BOOL, "noup5dgrad": _BOOL,
     "nostatfuse": _BOOL, "nokeepv": _BOOL, "nodirect": _BOOL,
-    "tile16": [("wide", 1), ("w", 1), ("narrow", 0), ("1", 0)],
-    "glds_spec": [("1", 1), ("2", 2)], "glds_nbuf": [("1", 1)],
     "nowgrad16s": _BOOL, "wgrad16s_minpix": [("100000", 100000), ("", 0)], "noglds16": _BOOL,
-    "nosmall": _BOOL, "nothin": _BOOL, "thinin2": _ON_UNLESS_0,
+    "nosmall": _BOOL, "nothin": _BOOL,
     "nowino": _BOOL, "nowinoup5": _BOOL,
     "wino_vec": [("1", 1), ("4", 4), ("3", 2), ("8", 2), ("-2", 2)], "wino_vec3": [("1", 1), ("4", 4), ("3", 2), ("0", 2)],
     "roctx": _BOOL,
-    "side_prio": [("1", 1), ("-1", -1)], "lane_prio": [("-1", -1), ("1", 1)],
-    "noucache": _BOOL, "act16": _ON_UNLESS_0, "co16": _ON_UNLESS_0, "side_stream": _ON_UNLESS_0, "capture_lanes": _BOOL,
+    "noucache": _BOOL, "act16": _ON_UNLESS_0, "co16": _ON_UNLESS_0, "side_stream": _ON_UNLESS_0,
     "keepv_budget_gb": [("128", 128), ("2.9", 2), ("0.5", 0)],      # (read back truncated; the engine uses the real value)
-    "prefill_lane": _ON_UNLESS_0,
 }
 # key -> [(value given to aclgan_tuning, value read back)]
 SET = {
@@ -140,10 +130,15 @@ e0 = ep()
 rc, prev, err = tune("no such key", 1)
 assert rc == -1 and prev == 12345 and "unknown key" in err and ep() == e0
 assert get("no such key") is None
+for key in %r:      # a retired experiment is an unknown key: a script that still sets it fails instead of measuring the default
+    e0 = ep()
+    rc, prev, err = tune(key, 1)
+    assert rc == -1 and prev == 12345 and "unknown key '" + key + "'" in err and ep() == e0, (key, rc, prev, err)
+    assert get(key) is None and "unknown key '" + key + "'" in L.aclgan_last_error().decode(), key
 assert L.aclgan_set_deterministic(1) == 0 and get("deterministic") == 1 and L.aclgan_get_deterministic() == 1
 assert L.aclgan_set_deterministic(0) == 0 and get("deterministic") == 0 and L.aclgan_get_deterministic() == 0 and ep() == e0
 out["ok"] = 1
-''' % (SET, sorted(set(SWITCHES) - set(SETTABLE)))
+''' % (SET, sorted(set(SWITCHES) - set(SETTABLE)), RETIRED)
     assert sorted(SET) == sorted(SETTABLE)
     assert _child(code) == {"ok": 1}
 
