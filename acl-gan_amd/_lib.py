@@ -59,6 +59,8 @@ ACT = {"none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
 NORM = {"none": 0, "in": 1, "adain": 2, "ln": 3, "sn": 4}
 DTYPE = {"fp32": 0, "bf16": 1, "fp16": 2}
 GROUP_GEN, GROUP_DIS, GROUP_SN_STATE = 0, 1, 2
+EMA_COPY, EMA_BLEND = 0, 1            # ACLGAN_EMA_*
+WEIGHTS_LIVE, WEIGHTS_EMA = 0, 1      # ACLGAN_WEIGHTS_*
 NETS = {"gen_AB": 0, "gen_BA": 1, "dis_A": 2, "dis_B": 3, "dis_2": 4}
 LOSS_NAMES = [
     "loss_gen_adv_A", "loss_gen_adv_B", "loss_gen_adv_2",
@@ -114,6 +116,9 @@ SIGNATURES = {
     "aclgan_bucket_schedule": (ci, [vp, ci, ci, ci, ci, ci, C.POINTER(ci), ci, C.POINTER(ci)]),
     "aclgan_zero_grad": (ci, [vp, ci, vp]),
     "aclgan_adam_step": (ci, [vp, ci, C.POINTER(Adam), ci, vp]),
+    "aclgan_bind_ema": (ci, [vp, ci, vp]),
+    "aclgan_adam_step_ema": (ci, [vp, ci, C.POINTER(Adam), ci, cf, ci, vp]),
+    "aclgan_set_forward_weights": (ci, [vp, ci]),
     "aclgan_gen_encode": (ci, [vp, ci, vp, ci, ci, ci, vp, vp, vp]),
     "aclgan_gen_decode": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp]),
     "aclgan_dis_forward": (ci, [vp, ci, vp, ci, ci, ci, C.POINTER(vp), vp]),
@@ -164,6 +169,7 @@ SIGNATURES = {
     "aclgan_avgpool3s2_fwd": (ci, [ci, ci, ci, ci, vp, vp, vp]),
     "aclgan_avgpool3s2_bwd": (ci, [ci, ci, ci, ci, vp, vp, ci, vp]),
     "aclgan_adam_flat": (ci, [vp, vp, vp, vp, i64, C.POINTER(Adam), ci, vp]),
+    "aclgan_adam_flat_ema": (ci, [vp, vp, vp, vp, vp, i64, C.POINTER(Adam), ci, cf, ci, vp]),
     "aclgan_linear_fwd": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp]),
     "aclgan_mlp3_fwd": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "aclgan_linear_bwd": (ci, [ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),

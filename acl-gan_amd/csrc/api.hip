@@ -430,6 +430,10 @@ int aclgan_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, co
     ACL_REQUIRE(p && g && m && v && opt, "adam: null buffer");
     return adam_flat(p, g, m, v, n, opt, step, (hipStream_t)stream);
 }
+int aclgan_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* opt, int step, float decay, int mode, void* stream) {
+    ACL_REQUIRE(p && g && m && v && opt, "adam: null buffer");
+    return adam_flat_ema(p, g, m, v, ema, n, opt, step, decay, mode, (hipStream_t)stream);
+}
 int aclgan_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, void* stream) {
     ACL_REQUIRE(src && dst, "layout: null buffer");
     return nchw_to_nhwc(src, dst, B, C, H, W, (hipStream_t)stream);

@@ -223,6 +223,8 @@ int positive_mask_diff(const float* a, int ca, const float* b, int cb, unsigned 
 int avgpool3s2_fwd(int B, int H, int W, int C, const float* x, float* y, hipStream_t st);
 int avgpool3s2_bwd(int B, int H, int W, int C, const float* dy, float* dx, int accumulate, hipStream_t st);
 int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, hipStream_t st);
+// the same launch with the exponential moving average of p as one more stream (mode: ACLGAN_EMA_COPY / ACLGAN_EMA_BLEND); p, m, v as adam_flat
+int adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode, hipStream_t st);
 int nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, hipStream_t st);
 int nhwc_to_nchw(const float* src, float* dst, int B, int C, int H, int W, hipStream_t st);
 int fill_zero(float* p, int64_t n, hipStream_t st);
@@ -285,6 +287,9 @@ int focus_loss_finish(const float* dec4, int64_t npix, const float* part, float 
 int focus_totals(const float* part, int64_t npix, int nmask, float* totals, hipStream_t st);
 // Adam under fp16 dynamic loss scaling: overflow scan, update with g/S (or skip), scale update -- all on the device
 int adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, float* state, int group, hipStream_t st);
+// ... with the average: a skipped update (overflow) leaves ema untouched together with p, m and v
+int adam_flat_scaled_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
+                         float* state, int group, hipStream_t st);
 
 
 // spectral normalisation (spectral.hip): one power iteration + normalised weight for up to SN_MAX_LAYERS Co x K matrices in four launches;

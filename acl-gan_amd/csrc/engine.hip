@@ -186,6 +186,14 @@ struct aclgan_ctx {
     unsigned short* w16[2] = {nullptr, nullptr};
     unsigned short* w16t[2] = {nullptr, nullptr};
     float* lscale = nullptr;
+    // averaged generator (aclgan_bind_ema / aclgan_set_forward_weights): the average lives in a caller-owned buffer laid out like the generator
+    // group's parameters.  read_ema is the selection of the call in flight: set by the forward-only entry points from fwd_weights, cleared by
+    // reset_step -- updates and dry runs read the live weights whatever the switch says.  Everything that reads a weight goes through
+    // weights(group): param() / pw() (fp32 pointers and the offsets into the 16-bit packs) and pack_params (what the packs are cast from).
+    float* ema = nullptr;
+    int fwd_weights = ACLGAN_WEIGHTS_LIVE;
+    bool read_ema = false;
+    const float* weights(int group) const { return group == ACLGAN_GROUP_GEN && read_ema ? ema : groups[group].param; }
     std::vector<int64_t> cv_off[2];          // conv tensors of each group: offset / Cout / taps / Cin (transposed pack)
     std::vector<int> cv_co[2], cv_taps[2], cv_ci[2];
     int trained = -1;          // group whose gradients this step produces (-1: forward only)
@@ -483,6 +491,7 @@ struct aclgan_ctx {
         top2 = 0;
         keep_total = 0;
         ucache.clear();
+        read_ema = false;
         for (int l = 0; l < MAXL; ++l) { lane_evs[l].clear(); hw[l] = 0; lane_dirty[l] = false; for (int m = 0; m < MAXL; ++m) seen[l][m] = 0; }
         ev_next = 0; cur_lane = 0; nlanes = 1; pass_seq = 0; cur_pass_id = -1;
         if (st0) { st = st0; st0 = nullptr; }
@@ -642,7 +651,7 @@ const float* aclgan_ctx::param(int group, int net, const std::string& key) const
     const Group& g = groups[group];
     auto it = g.index.find(std::string(NET_NAMES[net]) + "/" + key);
     if (it == g.index.end() || !g.param) return nullptr;
-    return g.param + g.tensors[it->second].offset;
+    return weights(group) + g.tensors[it->second].offset;
 }
 float* aclgan_ctx::gradp(int group, int net, const std::string& key) const {
     const Group& g = groups[group];
@@ -660,7 +669,7 @@ PW aclgan_ctx::pw(int group, int net, const std::string& key, bool with_bias) co
     p.w = param(group, net, key + ".weight"); p.dw = gradp(group, net, key + ".weight"); p.nw = numel_of(group, net, key + ".weight");
     if (with_bias) { p.b = param(group, net, key + ".bias"); p.db = gradp(group, net, key + ".bias"); p.nb = numel_of(group, net, key + ".bias"); }
     if (dtype != ACLGAN_DTYPE_FP32 && p.w && w16[group] && w16t[group]) {
-        const int64_t off = p.w - groups[group].param;
+        const int64_t off = p.w - weights(group);
         p.w16 = w16[group] + off; p.w16t = w16t[group] + off;
     }
     return p;
@@ -1392,13 +1401,14 @@ __global__ void dis_total_kernel(float* L, aclgan_hparams hp) {
 
 // Refresh the 16-bit weight packs from the fp32 master parameters (both groups: each update runs the other group's
 // networks forward / dgrad-only).  ~55 M elements read once, 2 x 2 bytes written: ~0.1 ms against a step of tens of ms,
-// and it makes the packs immune to whatever touched the flat buffers between calls (Adam, load_state_dict, broadcast).
+// and it makes the packs immune to whatever touched the flat buffers between calls (Adam, load_state_dict, broadcast) and to the
+// forward-weights switch: a forward-only call that reads the averaged generator packs from the average (aclgan_ctx::weights).
 static int pack_params(aclgan_ctx& c) {
     if (c.dtype == ACLGAN_DTYPE_FP32 || c.dry) return ACLGAN_OK;
     for (int g = 0; g < 2; ++g) {
         if (!c.w16[g] || !c.w16t[g]) { set_error("compute dtype is 16-bit but aclgan_bind_params16 was not called for group %d", g); return ACLGAN_EINVAL; }
-        CHK(cast_flat16(c.groups[g].param, c.w16[g], c.groups[g].numel, c.dtype, c.st));
-        CHK(transpose_flat16(c.groups[g].param, c.w16t[g], c.cv_off[g].data(), c.cv_co[g].data(), c.cv_taps[g].data(), c.cv_ci[g].data(),
+        CHK(cast_flat16(c.weights(g), c.w16[g], c.groups[g].numel, c.dtype, c.st));
+        CHK(transpose_flat16(c.weights(g), c.w16t[g], c.cv_off[g].data(), c.cv_co[g].data(), c.cv_taps[g].data(), c.cv_ci[g].data(),
                              (int)c.cv_off[g].size(), c.dtype, c.st));
     }
     return ACLGAN_OK;
@@ -1923,6 +1933,7 @@ int aclgan_step_algorithmic_bytes(aclgan_ctx* ctx, int which, int B, int H, int 
     c.peak = 0; c.peak2 = 0;
     if (rc) return rc;
     *out = c.alg_bytes + (4.0 + 28.0) * (double)c.groups[which].numel;    // + zero_grad + Adam (p, g, m, v read; p, m, v written)
+    if (which == ACLGAN_GROUP_GEN && c.ema) *out += 8.0 * (double)c.groups[which].numel;      // + the average read and written by the same launch
     return ACLGAN_OK;
 }
 // the matrix-pipe FLOPs of the same update as the kernels EXECUTE them (conv_exec_flops: the cost of the path every layer's launchers choose
@@ -2076,6 +2087,29 @@ int aclgan_adam_step(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int ste
     return adam_flat(g.param, g.grad, g.m, g.v, g.numel, opt, step, (hipStream_t)stream);
 }
 
+int aclgan_bind_ema(aclgan_ctx* ctx, int group, float* ema) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(group == ACLGAN_GROUP_GEN, "bind_ema: only the generator group (ACLGAN_GROUP_GEN) has an averaged copy; got group %d", group);
+    ctx->ema = ema;
+    if (!ema) ctx->fwd_weights = ACLGAN_WEIGHTS_LIVE;
+    return ACLGAN_OK;
+}
+int aclgan_adam_step_ema(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int step, float decay, int mode, void* stream) {
+    ACL_REQUIRE(ctx && opt, "bad ctx/opt");
+    ACL_REQUIRE(group == ACLGAN_GROUP_GEN && ctx->ema, "adam_step_ema: no averaged copy is bound for group %d (aclgan_bind_ema)", group);
+    Group& g = ctx->groups[group];
+    ACL_REQUIRE(g.param && g.grad && g.m && g.v, "param/grad/exp_avg/exp_avg_sq must all be bound");
+    if (ctx->lscale) return adam_flat_scaled_ema(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, ctx->lscale, group, (hipStream_t)stream);
+    return adam_flat_ema(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, (hipStream_t)stream);
+}
+int aclgan_set_forward_weights(aclgan_ctx* ctx, int which) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(which == ACLGAN_WEIGHTS_LIVE || which == ACLGAN_WEIGHTS_EMA, "set_forward_weights: %d is neither ACLGAN_WEIGHTS_LIVE nor ACLGAN_WEIGHTS_EMA", which);
+    ACL_REQUIRE(which == ACLGAN_WEIGHTS_LIVE || ctx->ema, "set_forward_weights: no averaged copy is bound (aclgan_bind_ema)");
+    ctx->fwd_weights = which;
+    return ACLGAN_OK;
+}
+
 // ---- forward-only entry points ----
 static int fwd_begin(aclgan_ctx* ctx, void* stream) {
     ACL_REQUIRE(ctx && ctx->ws, "bind a workspace first");
@@ -2083,6 +2117,7 @@ static int fwd_begin(aclgan_ctx* ctx, void* stream) {
     ctx->reset_step();
     // (peak2: the side stack's high-water mark of whatever ran before -- an update, a dry run -- is not this call's: a forward-only arena has no side stack)
     ctx->st = (hipStream_t)stream; ctx->dry = false; ctx->peak = 0; ctx->peak2 = 0; ctx->trained = -1;
+    ctx->read_ema = ctx->fwd_weights == ACLGAN_WEIGHTS_EMA;
     return ACLGAN_OK;
 }
 

@@ -209,25 +209,63 @@ int avgpool3s2_bwd(int B, int H, int W, int C, const float* dy, float* dx, int a
 }
 
 // ---- Adam (torch.optim.Adam with L2 weight decay, trainer.py:39-42) ----
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            int64_t n, float b1, float b2, float eps, float wd, float step_size, float inv_sqrt_bc2) {
+// One grid-stride pass of the update, shared by the four kernels below.  SCALED: the gradient carries the fp16 loss scale (inv = 1 / S).
+// EMA: one more stream in the same pass -- the exponential moving average of the parameters (8 B / element on top of the 28), written from
+// the p this launch has just computed: blend = d * ema + (1 - d) * p_new, copy = p_new (not d = 0: a non-finite old value would stay NaN;
+// copy does not read ema at all).
+template <bool SCALED, bool EMA>
+__device__ __forceinline__ void adam_pass(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                          float b1, float b2, float eps, float wd, float step_size, float inv_sqrt_bc2, float inv,
+                                          float* __restrict__ ema, float d, int blend) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float pv = p[i];
-        const float gv = fmaf(wd, pv, g[i]);
+        const float gv = fmaf(wd, pv, SCALED ? g[i] * inv : g[i]);
         const float mv = fmaf(b1, m[i], (1.f - b1) * gv);
         const float vv = fmaf(b2, v[i], (1.f - b2) * gv * gv);
         m[i] = mv; v[i] = vv;
-        p[i] = pv - step_size * mv / (sqrtf(vv) * inv_sqrt_bc2 + eps);
+        const float pn = pv - step_size * mv / (sqrtf(vv) * inv_sqrt_bc2 + eps);
+        p[i] = pn;
+        if (EMA) ema[i] = blend ? fmaf(d, ema[i], (1.f - d) * pn) : pn;
     }
 }
-int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, hipStream_t st) {
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            int64_t n, float b1, float b2, float eps, float wd, float step_size, float inv_sqrt_bc2) {
+    adam_pass<false, false>(p, g, m, v, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, 1.f, nullptr, 0.f, 0);
+}
+__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                int64_t n, float b1, float b2, float eps, float wd, float step_size, float inv_sqrt_bc2,
+                                float* __restrict__ ema, float d, int blend) {
+    adam_pass<false, true>(p, g, m, v, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, 1.f, ema, d, blend);
+}
+static int ema_args_ok(const float* ema, float decay, int mode) {
+    ACL_REQUIRE(ema, "adam (EMA): the average's buffer is null");
+    ACL_REQUIRE(mode == ACLGAN_EMA_COPY || mode == ACLGAN_EMA_BLEND, "adam (EMA): mode %d is neither ACLGAN_EMA_COPY nor ACLGAN_EMA_BLEND", mode);
+    ACL_REQUIRE(mode == ACLGAN_EMA_COPY || (decay >= 0.f && decay < 1.f), "adam (EMA): decay %g outside [0, 1)", (double)decay);
+    return ACLGAN_OK;
+}
+// ema == nullptr: the plain update (adam_kernel, the launch every caller without an average makes)
+static int adam_launch(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode, hipStream_t st) {
     ACL_REQUIRE(step >= 1, "adam: step must be >= 1");
     const double bc1 = 1.0 - pow((double)o->beta1, step), bc2 = 1.0 - pow((double)o->beta2, step);
     const int grid = (int)std::min<int64_t>(cdiv64(n, 256), 16384);
+    const float step_size = (float)(o->lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    if (ema) {
+        hipLaunchKernelGGL(adam_ema_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay,
+                           step_size, inv_sqrt_bc2, ema, decay, mode == ACLGAN_EMA_BLEND ? 1 : 0);
+        ACL_CHECK_LAUNCH("adam_ema_kernel");
+        return ACLGAN_OK;
+    }
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay,
-                       (float)(o->lr / bc1), (float)(1.0 / sqrt(bc2)));
+                       step_size, inv_sqrt_bc2);
     ACL_CHECK_LAUNCH("adam_kernel");
     return ACLGAN_OK;
+}
+int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, hipStream_t st) {
+    return adam_launch(p, g, m, v, nullptr, n, o, step, 0.f, ACLGAN_EMA_COPY, st);
+}
+int adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode, hipStream_t st) {
+    const int rc = ema_args_ok(ema, decay, mode);
+    return rc ? rc : adam_launch(p, g, m, v, ema, n, o, step, decay, mode, st);
 }
 
 // ---- Adam under fp16 dynamic loss scaling (state layout: include/aclgan_hip.h, aclgan_bind_loss_scale) ----
@@ -236,20 +274,24 @@ __global__ void grad_check_kernel(const float* __restrict__ g, int64_t n, float*
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) bad |= !isfinite(g[i]);
     if (bad) state[3] = 1.f;   // benign race: every writer stores the same value
 }
-__global__ void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                   int64_t n, float b1, float b2, float eps, float wd, float lr, int step_host, const float* __restrict__ state, int group) {
-    if (state[3] != 0.f) return;                   // overflow somewhere in this group's gradients: skip the update
+template <bool EMA>
+__device__ __forceinline__ void adam_scaled_pass(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                 float b1, float b2, float eps, float wd, float lr, int step_host, const float* __restrict__ state, int group,
+                                                 float* __restrict__ ema, float d, int blend) {
+    if (state[3] != 0.f) return;                   // overflow somewhere in this group's gradients: skip the update (p, m, v and the average stay)
     const int step = step_host - (int)state[4 + group];   // skipped updates do not advance Adam's bias correction
     const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
     const float step_size = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2)), inv = state[1];
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float pv = p[i];
-        const float gv = fmaf(wd, pv, g[i] * inv);
-        const float mv = fmaf(b1, m[i], (1.f - b1) * gv);
-        const float vv = fmaf(b2, v[i], (1.f - b2) * gv * gv);
-        m[i] = mv; v[i] = vv;
-        p[i] = pv - step_size * mv / (sqrtf(vv) * inv_sqrt_bc2 + eps);
-    }
+    adam_pass<true, EMA>(p, g, m, v, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, inv, ema, d, blend);
+}
+__global__ void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                   int64_t n, float b1, float b2, float eps, float wd, float lr, int step_host, const float* __restrict__ state, int group) {
+    adam_scaled_pass<false>(p, g, m, v, n, b1, b2, eps, wd, lr, step_host, state, group, nullptr, 0.f, 0);
+}
+__global__ void adam_scaled_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                       int64_t n, float b1, float b2, float eps, float wd, float lr, int step_host, const float* __restrict__ state, int group,
+                                       float* __restrict__ ema, float d, int blend) {
+    adam_scaled_pass<true>(p, g, m, v, n, b1, b2, eps, wd, lr, step_host, state, group, ema, d, blend);
 }
 __global__ void scale_update_kernel(float* state, int group) {
     state[7] = state[0];      // the scale the gradient buffers of THIS update carry (readable after the scale has moved on)
@@ -263,16 +305,32 @@ __global__ void scale_update_kernel(float* state, int group) {
     state[1] = 1.f / state[0];
     state[3] = 0.f;
 }
-int adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, float* state, int group, hipStream_t st) {
+// ema == nullptr: the plain loss-scaled update (adam_scaled_kernel)
+static int adam_scaled_launch(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
+                         float* state, int group, hipStream_t st) {
     ACL_REQUIRE(step >= 1 && state && (group == 0 || group == 1), "adam (loss-scaled): bad arguments");
     const int grid = (int)std::min<int64_t>(cdiv64(n, 256), 16384);
     hipLaunchKernelGGL(grad_check_kernel, dim3(grid), dim3(256), 0, st, g, n, state);
     ACL_CHECK_LAUNCH("grad_check_kernel");
-    hipLaunchKernelGGL(adam_scaled_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay, o->lr, step, state, group);
-    ACL_CHECK_LAUNCH("adam_scaled_kernel");
+    if (ema) {
+        hipLaunchKernelGGL(adam_scaled_ema_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay, o->lr, step, state, group,
+                           ema, decay, mode == ACLGAN_EMA_BLEND ? 1 : 0);
+        ACL_CHECK_LAUNCH("adam_scaled_ema_kernel");
+    } else {
+        hipLaunchKernelGGL(adam_scaled_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay, o->lr, step, state, group);
+        ACL_CHECK_LAUNCH("adam_scaled_kernel");
+    }
     hipLaunchKernelGGL(scale_update_kernel, dim3(1), dim3(1), 0, st, state, group);
     ACL_CHECK_LAUNCH("scale_update_kernel");
     return ACLGAN_OK;
+}
+int adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, float* state, int group, hipStream_t st) {
+    return adam_scaled_launch(p, g, m, v, nullptr, n, o, step, 0.f, ACLGAN_EMA_COPY, state, group, st);
+}
+int adam_flat_scaled_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
+                              float* state, int group, hipStream_t st) {
+    const int rc = ema_args_ok(ema, decay, mode);
+    return rc ? rc : adam_scaled_launch(p, g, m, v, ema, n, o, step, decay, mode, state, group, st);
 }
 
 // ---- layout conversion at the boundary ----

@@ -14,12 +14,13 @@ import ctypes as C
 import math
 import os
 from collections import OrderedDict
+from contextlib import contextmanager
 
 import torch
 
 from . import _lib as L
 
-__all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "dis_norm_from_config", "hparams_from_config"]
+__all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "dis_norm_from_config", "ema_from_config", "hparams_from_config"]
 
 DIS_NORMS = ("none", "sn")    # dis.norm values the library implements (sn: SpectralNorm, networks.py:360-361,538-600)
 
@@ -44,6 +45,23 @@ def arch_from_config(hp):
     return L.Arch(int(hp["input_dim_a"]), int(hp["input_dim_b"]), int(g["dim"]), int(g["mlp_dim"]), int(g["style_dim"]),
                   int(g["output_dim"]), int(g["n_downsample"]), int(g["n_res"]), int(d["dim"]), int(d["n_layer"]),
                   int(d["num_scales"]))
+
+
+def ema_from_config(hp):
+    """The averaged generator's keys (not in the reference) as (decay, start, display):
+    ema_decay   float in [0, 1), default 0 = off: no buffer, no extra call, the launches of a run without the keys;
+    ema_start   int >= 0, default 0: the generator updates 1 .. ema_start copy the weights into the average, later ones blend;
+    ema_display bool, default false: train.py's pictures are sampled from the average (needs ema_decay > 0)."""
+    decay, start, display = hp.get("ema_decay", 0), hp.get("ema_start", 0), hp.get("ema_display", False)
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (0 <= decay and C.c_float(decay).value < 1):
+        raise L.AclganError("ema_decay=%r: expected a number in [0, 1) (0 switches the averaged generator off)" % (decay,))
+    if isinstance(start, bool) or not isinstance(start, int) or start < 0:
+        raise L.AclganError("ema_start=%r: expected an integer >= 0" % (start,))
+    if not isinstance(display, bool):
+        raise L.AclganError("ema_display=%r: expected true or false" % (display,))
+    if display and not decay > 0:
+        raise L.AclganError("ema_display: true needs ema_decay > 0 (there is no averaged generator to sample from)")
+    return float(decay), start, display
 
 
 def hparams_from_config(hp):
@@ -73,9 +91,12 @@ class _Net:
             return flat.view(co, kh, kw, ci).permute(0, 3, 1, 2)
         return flat.view(*shp)
 
-    def named_parameters(self):
+    def _named_views(self, buf):
         for e in self._entries:
-            yield e["key"], self._view(e, self._t._param[self.group])
+            yield e["key"], self._view(e, buf)
+
+    def named_parameters(self):
+        return self._named_views(self._t._param[self.group])
 
     def named_grads(self):
         for e in self._entries:
@@ -85,8 +106,12 @@ class _Net:
         return [p for _, p in self.named_parameters()]
 
     def state_dict(self):
+        return self._state_dict_of(self._t._param[self.group])
+
+    def _state_dict_of(self, buf):
+        """the reference's state_dict with the parameters read from `buf` (the group's flat parameter buffer, or the generators' average)"""
         sd = OrderedDict()
-        params = OrderedDict((k, v.contiguous().clone()) for k, v in self.named_parameters())
+        params = OrderedDict((k, v.contiguous().clone()) for k, v in self._named_views(buf))
         bufs = self._buffers()
         # reference ordering: per module, parameters then buffers (SURVEY.md section 5)
         for k in self._t._ref_key_order(self.name, list(params.keys()), list(bufs.keys())):
@@ -233,6 +258,7 @@ class aclgan_Trainer:
         hp = hyperparameters
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.arch = arch_from_config(hp)
+        self._ema_decay, self._ema_start, self.ema_display = ema_from_config(hp)
         # compute dtype of the heavy convolutions (not in the reference, which is fp32 only): "fp32" | "bf16" | "fp16"
         self.compute_dtype = str(compute_dtype or hp.get("compute_dtype", "fp32"))
         if self.compute_dtype not in L.DTYPE:
@@ -343,7 +369,14 @@ class aclgan_Trainer:
         # (grad_scale(grp)); the two groups are updated at different live scales whenever one of them overflowed in between
         self._gscale = None if self._lscale is None else torch.zeros(2, dtype=torch.float32, device=self.device)
         self._last_grp = None
+        self._ema = None
+        self._fwd_ema = False
         self._setup_data_parallel()
+        # averaged generator (ema_decay > 0): one more flat buffer beside the generator group's, starting from this replica's weights
+        # (initialised and, data-parallel, already rank 0's); the generator's Adam launch keeps it up to date (aclgan_adam_step_ema)
+        if self._ema_decay > 0:
+            self._ema = self._param[L.GROUP_GEN].clone()
+            L.check(L.lib.aclgan_bind_ema(self._ctx, L.GROUP_GEN, L.ptr(self._ema)), "bind_ema")
 
     def __del__(self):
         try:
@@ -562,7 +595,11 @@ class aclgan_Trainer:
             o = self._opt[grp]
             o["steps"] += 1
             adam = L.Adam(self._current_lr(self._hp), o["beta1"], o["beta2"], o["eps"], o["weight_decay"])
-            L.check(L.lib.aclgan_adam_step(self._ctx, grp, C.byref(adam), o["steps"], st), "adam_step")   # opt.step()
+            if grp == L.GROUP_GEN and self._ema is not None:      # opt.step() with the average as one more stream of the same launch
+                mode = L.EMA_COPY if o["steps"] <= self._ema_start else L.EMA_BLEND
+                L.check(L.lib.aclgan_adam_step_ema(self._ctx, grp, C.byref(adam), o["steps"], self._ema_decay, mode, st), "adam_step_ema")
+            else:
+                L.check(L.lib.aclgan_adam_step(self._ctx, grp, C.byref(adam), o["steps"], st), "adam_step")   # opt.step()
         if which == "gen":
             self._publish_losses(0, 12)
         else:
@@ -620,6 +657,8 @@ class aclgan_Trainer:
         for grp in (L.GROUP_GEN, L.GROUP_DIS):
             for buf in (self._param[grp], self._m[grp], self._v[grp]):
                 broadcast_flat(buf)
+        if self._ema is not None:
+            broadcast_flat(self._ema)
         if self._tensors[L.GROUP_SN_STATE]:
             broadcast_flat(self._sn_state)   # spectral norm's u / v (not parameters, but every replica must start from the same)
         steps = torch.tensor([self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls], dtype=torch.int64, device=self.device)
@@ -707,8 +746,48 @@ class aclgan_Trainer:
                                                         L.ptr(out), B, H * W, self._st()), "focus_translation")
         return out
 
-    def sample(self, x_a, x_b):
-        """trainer.py:179-245: per-image eval forward; returns the reference's 9-tuple (focus branch) or 7-tuple (focus_loss == 0)."""
+    # ---- averaged generator (ema_decay > 0; not in the reference) ----
+    @property
+    def ema_updates(self):
+        """generator updates so far (Adam's step count; skipped fp16 updates included): the first ema_start of them copy, the rest blend"""
+        return self._opt[L.GROUP_GEN]["steps"]
+
+    def _require_ema(self, what):
+        if self._ema is None:
+            raise L.AclganError("%s: the averaged generator is off (set ema_decay in (0, 1))" % what)
+
+    @contextmanager
+    def ema_weights(self):
+        """Inside the block gen_AB / gen_BA .encode / .decode -- and so sample() and test.py's translate() -- read the averaged weights;
+        the updates keep reading (and writing) the live ones.  The previous selection comes back on exit, also on an exception."""
+        self._require_ema("ema_weights()")
+        prev = self._fwd_ema
+        self._select_forward_weights(True)
+        try:
+            yield self
+        finally:
+            self._select_forward_weights(prev)
+
+    def _select_forward_weights(self, ema):
+        L.check(L.lib.aclgan_set_forward_weights(self._ctx, L.WEIGHTS_EMA if ema else L.WEIGHTS_LIVE), "set_forward_weights")
+        self._fwd_ema = ema
+
+    def ema_state_dict(self):
+        """{'AB', 'BA'}: the averaged generators in the layout of gen_AB.state_dict() / gen_BA.state_dict() (what a gen_*.pt holds)"""
+        self._require_ema("ema_state_dict()")
+        return {"AB": self.gen_AB._state_dict_of(self._ema), "BA": self.gen_BA._state_dict_of(self._ema)}
+
+    def ema_reset(self):
+        """start the average again from the live weights"""
+        self._require_ema("ema_reset()")
+        self._ema.copy_(self._param[L.GROUP_GEN])
+
+    def sample(self, x_a, x_b, ema=False):
+        """trainer.py:179-245: per-image eval forward; returns the reference's 9-tuple (focus branch) or 7-tuple (focus_loss == 0).
+        ema=True: from the averaged generators (ema_weights())."""
+        if ema:
+            with self.ema_weights():
+                return self.sample(x_a, x_b)
         x_a = x_a.to(self.device, torch.float32)
         x_b = x_b.to(self.device, torch.float32)
         if not (self.focus_lam > 0):
@@ -802,6 +881,12 @@ class aclgan_Trainer:
             # 'step' above counts applied + skipped updates (the reference's own counter semantics: one per optimizer.step() call).
             opt["aclgan_loss_scale_state"] = self._lscale.cpu().clone()
         torch.save(opt, opt_name)
+        if self._ema is not None:
+            # the averaged generators, loadable wherever a gen_*.pt is (test.py --checkpoint).  The name holds neither "gen" nor "dis":
+            # _get_model_list (and the reference's, utils.py:211-220) matches by substring and takes the last name in sorted order
+            sd = self.ema_state_dict()
+            torch.save({"AB": cpu(sd["AB"]), "BA": cpu(sd["BA"]), "updates": self.ema_updates, "decay": self._ema_decay},
+                       os.path.join(snapshot_dir, "ema_%08d.pt" % (iterations + 1)))
 
     @staticmethod
     def _get_model_list(dirname, key):   # utils.py:211-220
@@ -829,6 +914,18 @@ class aclgan_Trainer:
         # calls self.step() instead and would resume one epoch later (iterations + 1) -- the pinned version is the one mirrored here
         # (ACLGAN_RESUME_SCHED_PLUS1=1 selects the torch >= 1.4 behaviour).
         self._sched_calls = iterations + (1 if os.environ.get("ACLGAN_RESUME_SCHED_PLUS1") == "1" else 0)
+        if self._ema is not None:
+            ema_name = os.path.join(checkpoint_dir, "ema_%08d.pt" % iterations)
+            if os.path.isfile(ema_name):
+                sd = torch.load(ema_name, map_location="cpu")
+                with torch.no_grad():
+                    for net, key in ((self.gen_AB, "AB"), (self.gen_BA, "BA")):
+                        for k, v in net._named_views(self._ema):
+                            v.copy_(sd[key][k].to(device=self.device, dtype=torch.float32))
+            else:
+                import warnings
+                warnings.warn("aclgan_Trainer.resume: %s not found; the averaged generator starts from the resumed weights" % ema_name)
+                self.ema_reset()
         self._hp = hyperparameters
         self._setup_data_parallel()
         print("Resume from iteration %d" % iterations)

@@ -65,6 +65,14 @@ extern "C" {
  * dis_opt): enumerated like a group by aclgan_group_numel / aclgan_tensor_count / aclgan_tensor_info, bound with aclgan_bind_sn_state */
 #define ACLGAN_GROUP_SN_STATE 2
 
+/* exponential moving average of the generator weights (NOT in the reference): what an Adam launch does to the average after it has
+ * written the new parameter p -- COPY: ema = p (the average has not started; the old value, finite or not, is not read);
+ * BLEND: ema = decay * ema + (1 - decay) * p.  And which weights the forward-only entry points read (aclgan_set_forward_weights). */
+#define ACLGAN_EMA_COPY 0
+#define ACLGAN_EMA_BLEND 1
+#define ACLGAN_WEIGHTS_LIVE 0
+#define ACLGAN_WEIGHTS_EMA 1
+
 /* networks (trainer.py:19-23) */
 #define ACLGAN_NET_GEN_AB 0
 #define ACLGAN_NET_GEN_BA 1
@@ -240,7 +248,8 @@ int aclgan_forward_workspace_bytes(aclgan_ctx* ctx, int B, int H, int W, size_t*
 /* ALGORITHMIC HBM bytes of one update at this batch shape (measurement support, SURVEY.md 8d / bench.py roofline.traffic):
  * every operator of the step (trainer.py:99-169 / 254-292: convolutions, norms, activations, blends, losses and their
  * backward) counted with its inputs read once and its outputs written once at their storage width, from a launch-free dry
- * run of the same scheduler; zero_grad (4 B / parameter) and Adam (28 B / parameter, trainer.py:170,293) included.
+ * run of the same scheduler; zero_grad (4 B / parameter) and Adam (28 B / parameter, trainer.py:170,293; 36 for the generators while
+ * aclgan_bind_ema holds a buffer) included.
  * which: 0 gen_update, 1 dis_update. */
 int aclgan_step_algorithmic_bytes(aclgan_ctx* ctx, int which, int B, int H, int W, double* out);
 /* Round 6: the matrix-pipe FLOPs the same update EXECUTES -- every convolution at the cost of the path its launchers choose at this shape,
@@ -293,6 +302,21 @@ int aclgan_zero_grad(aclgan_ctx* ctx, int group, void* stream);
 /* opt.step() (trainer.py:170,293): one fused kernel over the group's flat buffers; `step` is the
  * 1-based Adam step count used for bias correction */
 int aclgan_adam_step(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int step, void* stream);
+/* ---- averaged generator (NOT in the reference) ----
+ * aclgan_bind_ema: a caller-owned buffer of aclgan_group_numel(ctx, group) floats that holds the average, in the layout of the parameter
+ * buffer.  ACLGAN_GROUP_GEN only (ACLGAN_EINVAL for the discriminators); the caller initialises it; NULL unbinds and selects the live
+ * weights again.  While one is bound aclgan_step_algorithmic_bytes counts Adam at 36 B / generator parameter instead of 28.
+ * aclgan_adam_step_ema: aclgan_adam_step of that group (same scan / skip / scale update under a bound loss scale) with the average as one more
+ * stream of the same launch: mode ACLGAN_EMA_COPY or ACLGAN_EMA_BLEND with 0 <= decay < 1.  param, exp_avg, exp_avg_sq come out bit-identical
+ * to aclgan_adam_step's; an update skipped for an fp16 overflow leaves the average untouched as well.  aclgan_adam_step itself never touches
+ * the average, bound or not.
+ * aclgan_set_forward_weights: which generator weights aclgan_gen_encode / aclgan_gen_decode read (and the 16-bit packs are refreshed from):
+ * ACLGAN_WEIGHTS_LIVE (default) or ACLGAN_WEIGHTS_EMA (an error with no buffer bound).  aclgan_gen_update / aclgan_dis_update always read the
+ * live weights.  Nothing derived from the weights outlives a call (filter transforms live in the arena of one call, the packs are refreshed
+ * by every call), so the switch takes effect with the next call. */
+int aclgan_bind_ema(aclgan_ctx* ctx, int group, float* ema);
+int aclgan_adam_step_ema(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int step, float decay, int mode, void* stream);
+int aclgan_set_forward_weights(aclgan_ctx* ctx, int which);
 
 /* ---- forward-only entry points (test.py:55-70 / trainer.sample: encode / decode / D forward) ---- */
 /* AdaINGen.encode (networks.py:141-145): content (B,C,H/4,W/4) NCHW, style (B,style_dim) */
@@ -537,6 +561,10 @@ int aclgan_focus_loss(const float* dec4, int64_t npix, float delta, float upper,
 /* torch.optim.Adam over a flat buffer (trainer.py:39-42,170,293) */
 int aclgan_adam_flat(float* p, const float* g, float* m, float* v, int64_t n,
                      const aclgan_adam* opt, int step, void* stream);
+/* the same launch with the exponential moving average of p as one more stream (ema: n floats; mode ACLGAN_EMA_COPY / ACLGAN_EMA_BLEND,
+ * 0 <= decay < 1): p, m, v bit-identical to aclgan_adam_flat's */
+int aclgan_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                         const aclgan_adam* opt, int step, float decay, int mode, void* stream);
 
 /* NCHW <-> NHWC (boundary layout conversion) */
 int aclgan_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, void* stream);

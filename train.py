@@ -15,7 +15,8 @@ logs/<model>/losses.csv (the reference logs the same members to TensorBoard, tra
 
 Pictures (train.py:44-47,83-95): every image_save_iter iterations trainer.sample() runs on fixed test and train display images and
 outputs/<model>/images/gen_a2b_{test,train}_%08d.jpg and outputs/<model>/index.html are written; every image_display_iter iterations
-images/gen_a2b_train_current.jpg.  The picture is composed on the device (acl-gan_amd/visual.py, csrc/grid.hip); the host encodes the JPEG.
+images/gen_a2b_train_current.jpg; with `ema_display: true` (and `ema_decay` > 0) they show the averaged generators instead of the live ones.
+The picture is composed on the device (acl-gan_amd/visual.py, csrc/grid.hip); the host encodes the JPEG.
 
 Data parallel (not in the reference, which is single-GPU: train.py:42): launched as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 train.py --config ...
@@ -168,14 +169,14 @@ def main():
         if display is not None and image_due(iterations, config, "image_save_iter"):      # train.py:83-90
             train_a, train_b, test_a, test_b = display
             with torch.no_grad():
-                test_image_outputs = trainer.sample(test_a, test_b)
-                train_image_outputs = trainer.sample(train_a, train_b)
+                test_image_outputs = trainer.sample(test_a, test_b, ema=trainer.ema_display)
+                train_image_outputs = trainer.sample(train_a, train_b, ema=trainer.ema_display)
             visual.write_2images(test_image_outputs, display_size, image_directory, "test_%08d" % (iterations + 1))
             visual.write_2images(train_image_outputs, display_size, image_directory, "train_%08d" % (iterations + 1))
             visual.write_html(os.path.join(output_directory, "index.html"), iterations + 1, config["image_save_iter"], "images")
         if display is not None and image_due(iterations, config, "image_display_iter"):   # train.py:92-95
             with torch.no_grad():
-                image_outputs = trainer.sample(display[0], display[1])
+                image_outputs = trainer.sample(display[0], display[1], ema=trainer.ema_display)
             visual.write_2images(image_outputs, display_size, image_directory, "train_current")
         if is_main and snapshot_due(iterations, config):      # replicas are identical: rank 0's copy is THE checkpoint
             trainer.save(checkpoint_directory, iterations)
