@@ -61,6 +61,7 @@ DTYPE = {"fp32": 0, "bf16": 1, "fp16": 2}
 GROUP_GEN, GROUP_DIS, GROUP_SN_STATE = 0, 1, 2
 EMA_COPY, EMA_BLEND = 0, 1            # ACLGAN_EMA_*
 WEIGHTS_LIVE, WEIGHTS_EMA = 0, 1      # ACLGAN_WEIGHTS_*
+CARRY_OFF, CARRY_KEEP, CARRY_ADOPT = 0, 1, 2      # ACLGAN_CARRY_*
 NETS = {"gen_AB": 0, "gen_BA": 1, "dis_A": 2, "dis_B": 3, "dis_2": 4}
 LOSS_NAMES = [
     "loss_gen_adv_A", "loss_gen_adv_B", "loss_gen_adv_2",
@@ -141,6 +142,7 @@ SIGNATURES = {
     "aclgan_tuning": (ci, [C.c_char_p, ci, C.POINTER(ci)]),
     "aclgan_tuning_get": (ci, [C.c_char_p, C.POINTER(C.c_longlong)]),
     "aclgan_check_workspace": (ci, [vp, ci, ci, ci]),
+    "aclgan_ctx_carry_encodings": (ci, [vp, ci]),
     "aclgan_conv2d_fwd16s_stats_chunk": (ci, [C.POINTER(ConvDesc)]),
     "aclgan_conv2d_fwd16s_stats": (ci, [C.POINTER(ConvDesc), ci, vp, vp, vp, vp, ci, vp, vp]),
     "aclgan_conv2d_dgrad16s_scratch_bytes": (sz, [C.POINTER(ConvDesc)]),

@@ -15,6 +15,8 @@ int hip_fail(hipError_t e, const char* what);
 
 // kernel launches issued by this library since load (measurement support: aclgan_launch_count; bench.py reports launches per step)
 extern std::atomic<long long> g_launches;
+// content-encoder passes a gen_update adopted from the dis_update before it instead of running them (engine.hip; tuning key enc_reuse_hits)
+extern std::atomic<long long> g_enc_reuse_hits;
 
 #define ACL_CHECK_LAUNCH(what)                                           \
     do {                                                                 \

@@ -214,6 +214,47 @@ struct aclgan_ctx {
         }
     };
     std::map<NeedKey, size_t> need_cache;
+    // ---- Content encodings of x_a carried from dis_update into the following gen_update (aclgan_ctx_carry_encodings).
+    // Both updates open with content_encode(gen_AB, x_a) and content_encode(gen_BA, x_a); dis_update trains only the discriminators, so the
+    // gen_update that follows it on the same batch would recompute the same two passes bit for bit.  KEEP: dis_update puts every tensor the
+    // backward of those passes reads (conv outputs, block outputs, statistics, mask coefficients) into a CARRY REGION at the end of the
+    // workspace that reset_step() does not reclaim, and leaves one CarryBlock per conv_block.  ADOPT: gen_update builds the same activations
+    // and the same backward closures around those pointers and launches nothing for the two passes.
+    //   Region: grows down from the end of the workspace; while carry_res > 0 the main stack and the side stream's stack end below it
+    //   (lim()).  carry_res is per call: the keeping dis_update grows it, the adopting gen_update starts with the record's size, every
+    //   other call has the whole workspace.  The data are complete on the caller's stream when dis_update returns (lanes_join).
+    //   Key: shape, compute dtype, the x_a pointer, the workspace, the switch setting (tuning epoch, deterministic mode) and gen_epoch, which
+    //   every entry point that can change what the generators compute bumps.  One shot: the next update consumes or drops the record.
+    struct CarryBlock { float *in32, *co, *out, *mean, *rstd, *ss; int B, H, W, C, co_st, out_st; };
+    struct CarryRec {
+        bool valid = false;
+        int B = 0, H = 0, W = 0, dtype = 0, determ = 0;
+        const float* x_a = nullptr;
+        long long gen_epoch = 0, tune_epoch = 0;
+        char* ws = nullptr; size_t ws_bytes = 0, bytes = 0;
+        std::vector<CarryBlock> blocks[2];       // [0] encode(gen_AB, x_a), [1] encode(gen_BA, x_a)
+    };
+    CarryRec carry;
+    long long gen_epoch = 0;
+    int carry_arm = ACLGAN_CARRY_OFF;            // what the caller armed for the next update
+    int carry_call = ACLGAN_CARRY_OFF;           // mode of the update being built (dry runs: the mode being sized)
+    int carry_mode = ACLGAN_CARRY_OFF;           // mode of the pass being built: carry_call inside the two carried passes, OFF elsewhere
+    int carry_pass = 0; size_t carry_blk = 0;
+    bool carry_fail = false;                     // a kept pass met a layer it cannot carry: no record
+    size_t carry_res = 0;
+    int last_mode[2] = {ACLGAN_CARRY_OFF, ACLGAN_CARRY_OFF};      // mode of the last real gen_update / dis_update (the dry-run diagnostics mirror it)
+    void carry_drop() { carry.valid = false; ++gen_epoch; }
+    size_t lim() const { return carry_res ? ((ws_bytes - carry_res) & ~(size_t)255) : ws_bytes; }
+    void* alloc_carry(size_t bytes) {
+        const size_t need = carry_res + ((bytes + 255) & ~(size_t)255);
+        if (dry) { carry_res = need; return (void*)(uintptr_t)4096; }
+        // (both stacks' high-water marks of this step: kernels in flight may still use what the host has released)
+        if (peak + peak2 + need + 512 > ws_bytes) return nullptr;
+        carry_res = need;
+        return ws + ((ws_bytes - need) & ~(size_t)255);
+    }
+    void carry_pass_begin(int pass) { carry_mode = carry_call; carry_pass = pass; carry_blk = 0; }
+    void carry_pass_end() { carry_mode = ACLGAN_CARRY_OFF; }
     // ALGORITHMIC HBM bytes of the step being built (aclgan_step_algorithmic_bytes): every operator's inputs read once and
     // outputs written once at their storage width -- what a perfectly fused-per-operator implementation must move
     double alg_bytes = 0.0;
@@ -285,8 +326,8 @@ struct aclgan_ctx {
         if (dry) return (void*)(uintptr_t)4096;
         // the main stack's high-water mark of this step, not its current top: scratch the host has released may still be in use by
         // kernels in flight on a lane
-        if (peak + need + 256 > ws_bytes) return nullptr;
-        return ws + ((ws_bytes - need) & ~(size_t)255);
+        if (peak + need + 256 > lim()) return nullptr;
+        return ws + ((lim() - need) & ~(size_t)255);
     }
     int side_fork() {       // the side stream may start once everything enqueued on the current lane so far is done
         if (dry) return ACLGAN_OK;
@@ -505,7 +546,7 @@ struct aclgan_ctx {
         if (dry) return (void*)(uintptr_t)(a + 4096);   // fake, never dereferenced
         // the side stream's stack grows down from the end of the workspace and its kernels may still be running: the main stack
         // must stay below the deepest point that stack has reached in this step (an undersized workspace fails, it does not corrupt)
-        if (top + peak2 + 256 > ws_bytes) return nullptr;
+        if (top + peak2 + 256 > lim()) return nullptr;      // (lim(): below the carried encodings, if this call keeps or adopts any)
         return ws + a;
     }
     float* allocf(int64_t n) { return (float*)alloc((size_t)n * sizeof(float)); }
@@ -514,6 +555,16 @@ struct aclgan_ctx {
         Act* a = new Act();
         a->B = B; a->H = H; a->W = W; a->C = C; a->need_grad = need_grad; a->dt = st; a->gdt = st;
         a->d = (float*)alloc((size_t)a->numel() * (st ? 2 : 4));
+        if (need_grad) a->g = allocf(a->numel());
+        acts.push_back(a);
+        wrote(a);
+        return a;
+    }
+    // the same with the data at `d` (the carry region: kept or adopted encodings); the gradient still comes from the arena
+    Act* new_act_at(int B, int H, int W, int C, bool need_grad, int st, float* d) {
+        Act* a = new Act();
+        a->B = B; a->H = H; a->W = W; a->C = C; a->need_grad = need_grad; a->dt = st; a->gdt = st;
+        a->d = d;
         if (need_grad) a->g = allocf(a->numel());
         acts.push_back(a);
         wrote(a);
@@ -645,6 +696,8 @@ static void build_dis(Group& g, const std::string& net, int input_dim, const acl
 
 static const char* NET_NAMES[5] = {"gen_AB", "gen_BA", "dis_A", "dis_B", "dis_2"};
 
+std::atomic<long long> g_enc_reuse_hits{0};      // encoder passes adopted so far (tuning key enc_reuse_hits)
+
 }  // namespace aclgan
 
 const float* aclgan_ctx::param(int group, int net, const std::string& key) const {
@@ -724,33 +777,67 @@ static int conv_block(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int Co,
     const bool a16 = h16 && c.act16();
     const bool s_bwd = a16 && f16 && d16 && w16 && conv16s_ok(g, 1);                 // backward on the 16-bit-storage kernels
     const bool s_fwd = a16 && f16 && conv16s_ok(g, 0) && in->dt != 0;                 // forward on the LDS-DMA kernel
-    if (in->dt != 0 && !(f16 && (w16 || !train_w))) {
+    // carried encodings (aclgan_ctx: CarryRec).  keep: this block's tensors go to the carry region and a CarryBlock says where; everything the
+    // backward of the adopting gen_update depends on is decided as that update decides it (tw).  adopt: the tensors are the kept ones, no launch.
+    const bool keep = c.carry_mode == ACLGAN_CARRY_KEEP, adopt = c.carry_mode == ACLGAN_CARRY_ADOPT, carried = keep || adopt;
+    const bool tw = train_w || keep;
+    aclgan_ctx::CarryBlock cb_dry = {};
+    aclgan_ctx::CarryBlock* cb = &cb_dry;
+    if (carried && !c.dry) {
+        std::vector<aclgan_ctx::CarryBlock>& blocks = c.carry.blocks[c.carry_pass];
+        if (keep) { blocks.push_back(cb_dry); cb = &blocks.back(); }
+        else {
+            if (c.carry_blk >= blocks.size()) { set_error("conv_block: the kept encodings hold no block %zu", c.carry_blk); return ACLGAN_EINVAL; }
+            cb = &blocks[c.carry_blk++];
+        }
+    }
+    auto carry_buf = [&](float* aclgan_ctx::CarryBlock::*slot, size_t bytes) -> float* {
+        if (adopt && !c.dry) return cb->*slot;
+        float* p = (float*)c.alloc_carry(bytes);      // (an adopting dry run reserves what the keeping call will have written)
+        cb->*slot = p;
+        return p;
+    };
+    if (in->dt != 0 && !(f16 && (w16 || !tw))) {
         // a 16-bit activation reaches a layer whose forward or weight-gradient kernel only reads fp32 (odd widths of reduced test
         // networks: Cout or Cin a multiple of 32 but not of 64): one fp32 copy serves both; the input gradient goes to the original
-        Act* in32 = c.new_act(in->B, in->H, in->W, in->C, false, 0);
+        Act* in32 = carried ? c.new_act_at(in->B, in->H, in->W, in->C, false, 0, carry_buf(&aclgan_ctx::CarryBlock::in32, (size_t)in->numel() * 4))
+                            : c.new_act(in->B, in->H, in->W, in->C, false, 0);
         NEED(in32->d);
-        RUN(cast_storage(in->d, in->dt, in32->d, 0, in->numel(), c.st));
+        if (!adopt) RUN(cast_storage(in->d, in->dt, in32->d, 0, in->numel(), c.st));
         in = in32;                                // data source of this block; gradients still go to the original (gin)
     }
     const int out_st = (a16 && Co % 64 == 0 && out16) ? dt : 0;
     const int co_st = has_norm ? ((s_bwd && sw(SW_CO16)) ? dt : 0) : ((f16 || !out_st) ? out_st : 0);
-    Act* co = c.new_act(g.B, g.Ho, g.Wo, Co, want_grad, co_st);
+    const size_t co_bytes = (size_t)g.B * g.Ho * g.Wo * Co * (co_st ? 2 : 4), out_bytes = (size_t)g.B * g.Ho * g.Wo * Co * (out_st ? 2 : 4);
+    if (adopt && !c.dry && (cb->B != g.B || cb->H != g.Ho || cb->W != g.Wo || cb->C != Co || cb->co_st != co_st || cb->out_st != out_st)) {
+        set_error("conv_block: the kept encodings do not match this layer (%d x %d x %d x %d)", g.B, g.Ho, g.Wo, Co);
+        return ACLGAN_EINVAL;
+    }
+    if (keep) { cb->B = g.B; cb->H = g.Ho; cb->W = g.Wo; cb->C = Co; cb->co_st = co_st; cb->out_st = out_st; }
+    Act* co = carried ? c.new_act_at(g.B, g.Ho, g.Wo, Co, want_grad, co_st, carry_buf(&aclgan_ctx::CarryBlock::co, co_bytes))
+                      : c.new_act(g.B, g.Ho, g.Wo, Co, want_grad, co_st);
     NEED(co->d); if (want_grad) NEED(co->g);
     Act* out = co;
     float *mean = nullptr, *rstd = nullptr, *ss = nullptr;
     const int HW = g.Ho * g.Wo;
     if (has_norm) {
-        out = c.new_act(g.B, g.Ho, g.Wo, Co, want_grad, out_st);
+        out = carried ? c.new_act_at(g.B, g.Ho, g.Wo, Co, want_grad, out_st, carry_buf(&aclgan_ctx::CarryBlock::out, out_bytes))
+                      : c.new_act(g.B, g.Ho, g.Wo, Co, want_grad, out_st);
         NEED(out->d); if (want_grad) NEED(out->g);
         const int nstat = ns.kind == ACLGAN_NORM_LN ? g.B : g.B * Co;
-        mean = c.allocf(nstat); rstd = c.allocf(nstat);
+        if (carried) { mean = carry_buf(&aclgan_ctx::CarryBlock::mean, (size_t)nstat * 4); rstd = carry_buf(&aclgan_ctx::CarryBlock::rstd, (size_t)nstat * 4); }
+        else { mean = c.allocf(nstat); rstd = c.allocf(nstat); }
         NEED(mean); NEED(rstd);
         // the fused coefficients of the apply stay until the backward: its ReLU mask is then the sign of the same fmaf(x, scale, shift), and
         // neither backward pass reads y (2 of 6 / 1 of 4 tensor reads of the reduce / apply of every activated norm layer)
-        if (want_grad && (act == ACLGAN_ACT_RELU || act == ACLGAN_ACT_LRELU) && sw(SW_NORM_MASK)) { ss = c.allocf((int64_t)2 * g.B * Co); NEED(ss); }
+        if ((want_grad || keep) && (act == ACLGAN_ACT_RELU || act == ACLGAN_ACT_LRELU) && sw(SW_NORM_MASK)) {
+            ss = carried ? carry_buf(&aclgan_ctx::CarryBlock::ss, (size_t)2 * g.B * Co * 4) : c.allocf((int64_t)2 * g.B * Co);
+            NEED(ss);
+        }
         co->gdt = s_bwd ? dt : 0;             // read by this layer's dgrad / wgrad kernels
     } else if (out_st && !co_st) {            // an fp32-only kernel (image-side first layers) feeding 16-bit consumers: one conversion pass
-        out = c.new_act(g.B, g.Ho, g.Wo, Co, want_grad, out_st);
+        out = carried ? c.new_act_at(g.B, g.Ho, g.Wo, Co, want_grad, out_st, carry_buf(&aclgan_ctx::CarryBlock::out, out_bytes))
+                      : c.new_act(g.B, g.Ho, g.Wo, Co, want_grad, out_st);
         NEED(out->d); if (want_grad) NEED(out->g);
         out->gdt = 0;                         // this layer's backward kernels read fp32
     } else {
@@ -761,18 +848,22 @@ static int conv_block(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int Co,
     // until the tape has run: 75 MB per ResBlock convolution at 256x256 B=8, ~6 GB per update) instead of recomputing it
     // Bounded: the kept transforms of one update may take at most ACLGAN_KEEPV_BUDGET_GB of the arena (default 64 GB of the 288 GB; 256x256
     // B=8 needs 6.5 GB, 512x512 B=4 13 GB, B=32 26 GB); beyond it a layer's weight gradient recomputes V (same result bit for bit).
+    // (an adopted block has no forward that could leave V: its weight gradient recomputes it, as beyond the budget.  The forward itself does not
+    //  depend on keeping V: conv_wino_keep_bytes offers it only where neither the fused kernel nor the bf16x3 GEMM runs, i.e. where the
+    //  three-launch fp32 pipeline runs either way, and the encoders have no sub-pixel layer)
     float* keepV = nullptr;
-    if (train_w && !f16 && !w16) {
+    if (train_w && !adopt && !f16 && !w16) {
         const size_t kb = conv_fwd_keep_bytes(g);
         if (kb && c.keep_total + kb <= (size_t)(sw_real(SW_KEEPV_BUDGET_GB) * 1073741824.0) + 1) { keepV = (float*)c.alloc(kb); NEED(keepV); c.keep_total += kb; }
     }
     const size_t ubytes = f16 ? 0 : conv_wino_u_bytes(g);          // fp32 Winograd layer: its filter transform is cached per update
-    if (ubytes && c.ucache_reserve(W.w, g.up ? 2 : 0, ubytes)) { set_error("workspace too small (filter-transform cache)"); return ACLGAN_ENOMEM; }
+    if (ubytes && !adopt && c.ucache_reserve(W.w, g.up ? 2 : 0, ubytes)) { set_error("workspace too small (filter-transform cache)"); return ACLGAN_ENOMEM; }
     const double es_in = in->dt ? 2.0 : 4.0, es_co = co->dt ? 2.0 : 4.0, es_out = out->dt ? 2.0 : 4.0, es_w = f16 ? 2.0 : 4.0;
-    c.count(es_in * (double)in->numel() + es_w * (double)Co * g.K + 4.0 * Co + es_co * (double)co->numel());             // conv: x, w, bias -> y
-    c.exec_flops += conv_exec_flops(g, 0, f16);
-    if (out != co) c.count((es_co + es_out) * (double)co->numel() + ((has_norm && residual) ? (residual->dt ? 2.0 : 4.0) * (double)co->numel() : 0.0));   // norm+act(+residual) / conversion: y -> out
+    if (!adopt) c.count(es_in * (double)in->numel() + es_w * (double)Co * g.K + 4.0 * Co + es_co * (double)co->numel());             // conv: x, w, bias -> y
+    if (!adopt) c.exec_flops += conv_exec_flops(g, 0, f16);
+    if (out != co && !adopt) c.count((es_co + es_out) * (double)co->numel() + ((has_norm && residual) ? (residual->dt ? 2.0 : 4.0) * (double)co->numel() : 0.0));   // norm+act(+residual) / conversion: y -> out
     const size_t mark = c.top;
+    if (!adopt) {      // (an adopted block: the forward below ran in the dis_update that kept it)
     // normalisation statistics from the conv epilogue where the forward kernel offers them (Winograd output transform)
     const int schunk = !has_norm ? 0 : (s_fwd ? conv_fwd16s_stats_chunk(g) : (!f16 ? conv_fwd_stats_chunk(g) : 0));
     float* stats = nullptr;
@@ -795,6 +886,7 @@ static int conv_block(aclgan_ctx& c, const PW& W, bool train_w, Act* in, int Co,
         RUN(norm_fwd(ns.kind, act, g.B, HW, Co, co->d, ns.w, ns.b, ns.w_stride, residual ? residual->d : nullptr, out->d, mean, rstd, scr, c.st, stats, schunk, &nst, ss));
     } else if (out != co) {
         RUN(cast_storage(co->d, co->dt, out->d, out->dt, co->numel(), c.st));
+    }
     }
     c.top = mark;
     *out_p = out;
@@ -975,7 +1067,7 @@ static int prefill_on_side_lane(aclgan_ctx& c, int B, int H, int W, bool train) 
 
 // ContentEncoder.forward (networks.py:230-245)
 static int content_encode(aclgan_ctx& c, int net, bool train, Act* x, Act** out) {
-    PassScope pass(c, net, "encode");
+    PassScope pass(c, net, c.carry_mode == ACLGAN_CARRY_ADOPT ? "encode(adopted)" : "encode");      // (adopted: a range without kernels)
     const aclgan_arch& a = c.arch;
     char buf[160];
     NormSpec in_; in_.kind = ACLGAN_NORM_IN;
@@ -1557,10 +1649,15 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     const int L0 = 0, L1 = 1, L2 = c.nlanes > 2 ? 2 : 1, LS = c.nlanes > 2 ? 2 : 0;
 #define PASS(expr) do { CHK(expr); CHK(c.mark()); } while (0)
     CHK(c.mark());                                                    // (the preamble: inputs, noise, filter transforms)
+    // (carry_call ADOPT: the two passes below were run by the dis_update before this call -- conv_block builds their activations and backward
+    //  closures around the kept tensors and launches nothing)
     CHK(c.set_lane(L0));
-    PASS(content_encode(c, AB, true, xa, &c1));                      // trainer.py:103 (style dropped)
+    c.carry_pass_begin(0);
+    { const int rc = content_encode(c, AB, true, xa, &c1); c.carry_pass_end(); CHK(rc); } CHK(c.mark());      // trainer.py:103 (style dropped)
     CHK(c.set_lane(L1));
-    PASS(content_encode(c, BA, true, xa, &c2));                      // trainer.py:104
+    c.carry_pass_begin(1);
+    { const int rc = content_encode(c, BA, true, xa, &c2); c.carry_pass_end(); CHK(rc); } CHK(c.mark());      // trainer.py:104
+    if (c.carry_call == ACLGAN_CARRY_ADOPT && !c.dry) { c.carry.valid = false; g_enc_reuse_hits += 2; }      // one shot
     PASS(style_encode(c, BA, true, xa, &s2));
     CHK(c.set_lane(L0));
     PASS(decode(c, AB, true, c1, z1, &dB4)); CHK(zero_grad_of(c, dB4));   // trainer.py:108
@@ -1693,10 +1790,13 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     // dis_B (which needs only x_B_fake) next to the second half of the chain; a third lane takes the coarser discriminator scales
     const int L0 = 0, L1 = 1, L2 = c.nlanes > 2 ? 2 : 1, LS = c.nlanes > 2 ? 2 : 0;
     CHK(c.mark());
+    // (carry_call KEEP: the two passes leave their tensors in the carry region for the gen_update that follows)
     CHK(c.set_lane(L0));
-    PASS(content_encode(c, AB, false, xa, &c1));
+    c.carry_pass_begin(0);
+    { const int rc = content_encode(c, AB, false, xa, &c1); c.carry_pass_end(); CHK(rc); } CHK(c.mark());
     CHK(c.set_lane(L1));
-    PASS(content_encode(c, BA, false, xa, &c2));
+    c.carry_pass_begin(1);
+    { const int rc = content_encode(c, BA, false, xa, &c2); c.carry_pass_end(); CHK(rc); } CHK(c.mark());
     CHK(c.set_lane(L0));
     PASS(decode(c, AB, false, c1, z1, &dB4));
     PASS(blend(c, dB4, xa, nullptr, &xB, nullptr, c.new_view(jB, 0, B), nullptr));
@@ -1821,11 +1921,13 @@ int aclgan_debug_mask_info(const aclgan_ctx* ctx, int index, int* dims4, long lo
 int aclgan_set_compute_dtype(aclgan_ctx* ctx, int dtype) {
     ACL_REQUIRE(ctx && dtype >= ACLGAN_DTYPE_FP32 && dtype <= ACLGAN_DTYPE_FP16, "bad ctx / dtype %d", dtype);
     ctx->dtype = dtype;
+    ctx->carry_drop();
     return ACLGAN_OK;
 }
 int aclgan_bind_params16(aclgan_ctx* ctx, int group, void* w16, void* w16t) {
     ACL_REQUIRE(ctx && group >= 0 && group <= 1, "bad ctx/group");
     ctx->w16[group] = (unsigned short*)w16; ctx->w16t[group] = (unsigned short*)w16t;
+    ctx->carry_drop();
     return ACLGAN_OK;
 }
 int aclgan_bind_loss_scale(aclgan_ctx* ctx, float* state) {
@@ -1858,6 +1960,7 @@ int aclgan_bind_params(aclgan_ctx* ctx, int group, float* param, float* grad, fl
     ACL_REQUIRE(param, "param buffer is null");
     Group& g = ctx->groups[group];
     g.param = param; g.grad = grad; g.m = exp_avg; g.v = exp_avg_sq;
+    ctx->carry_drop();
     return ACLGAN_OK;
 }
 int aclgan_bind_sn_state(aclgan_ctx* ctx, float* state) {
@@ -1868,19 +1971,23 @@ int aclgan_bind_sn_state(aclgan_ctx* ctx, float* state) {
 }
 
 // bytes one update needs (which: 0 gen_update, 1 dis_update) with the switches as they are now: a dry run of the same scheduler
-static int update_need_bytes(aclgan_ctx& c, int which, int B, int H, int W, size_t* out) {
+// carry: ACLGAN_CARRY_OFF, or the mode this update would run in (0 gen_update adopts, 1 dis_update keeps) -- the carried encodings then
+// take their own region at the end of the workspace, on top of the two stacks
+static int update_need_bytes(aclgan_ctx& c, int which, int B, int H, int W, size_t* out, int carry = ACLGAN_CARRY_OFF) {
     aclgan_hparams hp;
     memset(&hp, 0, sizeof hp);
     hp.focus_loss = c.arch.gen_output_dim == 4 ? 1.f : 0.f; hp.alpha = 1.f;      // (the branch the architecture can run: gen.output_dim 4 = focus, 3 = non-focus)
     c.reset_step();
     c.dry = true; c.peak = 0; c.peak2 = 0; c.trained = -1;
+    c.carry_call = carry; c.carry_res = 0;
     const aclgan_bucket_fn keep = c.bucket_fn;
     c.bucket_fn = nullptr;
     const int rc = which == 0 ? gen_update_impl(c, nullptr, nullptr, nullptr, B, H, W, hp, nullptr)
                               : dis_update_impl(c, nullptr, nullptr, nullptr, B, H, W, hp, nullptr);
     c.bucket_fn = keep;
     c.dry = false; c.trained = -1;
-    *out = c.peak + c.peak2 + 512;
+    *out = c.peak + c.peak2 + 512 + (c.carry_res ? c.carry_res + 256 : 0);
+    c.carry_call = ACLGAN_CARRY_OFF; c.carry_res = 0;
     c.reset_step();
     c.peak = 0; c.peak2 = 0;      // a dry run leaves no allocator state behind (a stale side-stack mark made later forward-only calls fail spuriously)
     return rc;
@@ -1890,12 +1997,14 @@ int aclgan_workspace_bytes(aclgan_ctx* ctx, int B, int H, int W, size_t* out) {
     aclgan_ctx& c = *ctx;
     ACL_REQUIRE(c.groups[0].param && c.groups[1].param, "bind parameters first");
     size_t best = 0;
-    for (int which = 0; which < 2; ++which) {
-        size_t pk = 0;
-        const int rc = update_need_bytes(c, which, B, H, W, &pk);
-        if (rc) return rc;
-        if (pk > best) best = pk;
-    }
+    // (enc_reuse on: room for the carried encodings too, whether or not the caller ever arms them)
+    for (int which = 0; which < 2; ++which)
+        for (int carry = 0; carry <= (sw(SW_ENC_REUSE) ? 1 : 0); ++carry) {
+            size_t pk = 0;
+            const int rc = update_need_bytes(c, which, B, H, W, &pk, !carry ? ACLGAN_CARRY_OFF : which == 0 ? ACLGAN_CARRY_ADOPT : ACLGAN_CARRY_KEEP);
+            if (rc) return rc;
+            if (pk > best) best = pk;
+        }
     *out = best + 4096;
     return ACLGAN_OK;
 }
@@ -1923,12 +2032,14 @@ int aclgan_step_algorithmic_bytes(aclgan_ctx* ctx, int which, int B, int H, int 
     hp.focus_loss = c.arch.gen_output_dim == 4 ? 1.f : 0.f; hp.alpha = 1.f;      // (the branch the architecture can run: gen.output_dim 4 = focus, 3 = non-focus)
     c.reset_step();
     c.dry = true; c.peak = 0; c.trained = which; c.alg_bytes = 0.0; c.exec_flops = 0.0;
+    c.carry_call = c.last_mode[which]; c.carry_res = 0;      // (as the last real call of this update ran: an adopting gen_update executes two passes less)
     const aclgan_bucket_fn keep = c.bucket_fn;
     c.bucket_fn = nullptr;
     const int rc = which == 0 ? gen_update_impl(c, nullptr, nullptr, nullptr, B, H, W, hp, nullptr)
                               : dis_update_impl(c, nullptr, nullptr, nullptr, B, H, W, hp, nullptr);
     c.bucket_fn = keep;
     c.dry = false; c.trained = -1;
+    c.carry_call = ACLGAN_CARRY_OFF; c.carry_res = 0;
     c.reset_step();
     c.peak = 0; c.peak2 = 0;
     if (rc) return rc;
@@ -1985,6 +2096,17 @@ int aclgan_forward_workspace_bytes(aclgan_ctx* ctx, int B, int H, int W, size_t*
 int aclgan_bind_workspace(aclgan_ctx* ctx, void* workspace, size_t bytes) {
     ACL_REQUIRE(ctx, "null ctx");
     ctx->ws = (char*)workspace; ctx->ws_bytes = bytes;
+    ctx->carry_drop();
+    return ACLGAN_OK;
+}
+
+// Arm the next update (one shot).  ACLGAN_CARRY_KEEP: the next aclgan_dis_update keeps the content encodings of its x_a.  ACLGAN_CARRY_ADOPT: the
+// next aclgan_gen_update may adopt them -- the caller's assertion that the CONTENTS of x_a have not changed since that dis_update; the library
+// checks the rest (shape, dtype, the x_a pointer, the workspace, the switches, and that nothing wrote the generator parameters in between).
+int aclgan_ctx_carry_encodings(aclgan_ctx* ctx, int mode) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(mode == ACLGAN_CARRY_OFF || mode == ACLGAN_CARRY_KEEP || mode == ACLGAN_CARRY_ADOPT, "carry_encodings: mode %d is none of ACLGAN_CARRY_OFF / KEEP / ADOPT", mode);
+    ctx->carry_arm = mode;
     return ACLGAN_OK;
 }
 
@@ -1996,22 +2118,49 @@ static int step_common(aclgan_ctx* ctx, const float* x_a, const float* x_b, cons
     ACL_REQUIRE(ctx->groups[group_trained].grad, "gradient buffer of the trained group is not bound");
     // the bound workspace against this update's need (a dry run, cached per shape / dtype / switch setting): an undersized workspace is
     // refused here, before anything is enqueued (the allocator checks every request as well)
+    // carried encodings: what the caller armed holds for this call only.  dis_update keeps when armed; gen_update adopts when armed and the
+    // record's key is this call's.  Never under stream capture (a graph has no cross-call state), while masks are being recorded (they are
+    // logged at forward time), with a fault injected, or with enc_reuse 0.  Whatever happens, the record does not outlive this call.
+    int carry = ctx->carry_arm;
+    ctx->carry_arm = ACLGAN_CARRY_OFF;
+    if (carry != (group_trained == 0 ? ACLGAN_CARRY_ADOPT : ACLGAN_CARRY_KEEP) || !sw(SW_ENC_REUSE) || ctx->mask_dst || sw(SW_FAULT_AT) >= 0) carry = ACLGAN_CARRY_OFF;
+    if (carry) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) { (void)hipGetLastError(); carry = ACLGAN_CARRY_OFF; }
+        else if (cs != hipStreamCaptureStatusNone) carry = ACLGAN_CARRY_OFF;
+    }
+    if (carry == ACLGAN_CARRY_ADOPT) {
+        const aclgan_ctx::CarryRec& r = ctx->carry;
+        if (!(r.valid && r.B == B && r.H == H && r.W == W && r.dtype == ctx->dtype && r.x_a == x_a && r.gen_epoch == ctx->gen_epoch &&
+              r.tune_epoch == tuning_epoch() && r.determ == sw(SW_DETERMINISTIC) && r.ws == ctx->ws && r.ws_bytes == ctx->ws_bytes))
+            carry = ACLGAN_CARRY_OFF;
+    }
+    if (carry != ACLGAN_CARRY_ADOPT) ctx->carry.valid = false;
+    // the bound workspace against this update's need (a dry run, cached per shape / dtype / switch setting): an undersized workspace is
+    // refused here, before anything is enqueued (the allocator checks every request as well)
     if (check_shape(*ctx, B, H, W) == ACLGAN_OK) {
-        const aclgan_ctx::NeedKey key{group_trained, B, H, W, ctx->dtype, tuning_epoch(), sw(SW_DETERMINISTIC), ctx->bucket_elems > 0 ? 1 : 0};
-        auto it = ctx->need_cache.find(key);
-        if (it == ctx->need_cache.end()) {
-            size_t need = 0;
-            const int rc = update_need_bytes(*ctx, group_trained, B, H, W, &need);
-            if (rc) return rc;
-            it = ctx->need_cache.emplace(key, need).first;
-        }
-        if (it->second > ctx->ws_bytes) {
+        for (;;) {
+            const aclgan_ctx::NeedKey key{group_trained, B, H, W, ctx->dtype, tuning_epoch(), sw(SW_DETERMINISTIC), (ctx->bucket_elems > 0 ? 1 : 0) | (carry << 1)};
+            auto it = ctx->need_cache.find(key);
+            if (it == ctx->need_cache.end()) {
+                size_t need = 0;
+                const int rc = update_need_bytes(*ctx, group_trained, B, H, W, &need, carry);
+                if (rc) return rc;
+                it = ctx->need_cache.emplace(key, need).first;
+            }
+            if (it->second <= ctx->ws_bytes) break;
+            // (a workspace sized without the carry region: the update runs, it just keeps / adopts nothing)
+            if (carry) { carry = ACLGAN_CARRY_OFF; ctx->carry.valid = false; continue; }
             set_error("workspace too small: bound %zu bytes, this update needs %zu (aclgan_workspace_bytes)", ctx->ws_bytes, it->second);
             return ACLGAN_ENOMEM;
         }
-    }
+    } else carry = ACLGAN_CARRY_OFF;
     ctx->reset_step();
     ctx->st = (hipStream_t)stream; ctx->dry = false; ctx->peak = 0; ctx->peak2 = 0; ctx->trained = group_trained;
+    ctx->carry_call = carry; ctx->carry_mode = ACLGAN_CARRY_OFF; ctx->carry_fail = false;
+    ctx->carry_res = carry == ACLGAN_CARRY_ADOPT ? ctx->carry.bytes : 0;
+    if (carry == ACLGAN_CARRY_KEEP) { ctx->carry.blocks[0].clear(); ctx->carry.blocks[1].clear(); }
+    ctx->last_mode[group_trained] = carry;
     return ACLGAN_OK;
 }
 
@@ -2024,6 +2173,8 @@ int aclgan_gen_update(aclgan_ctx* ctx, const float* x_a, const float* x_b, const
     rc = gen_update_impl(*ctx, x_a, x_b, z, B, H, W, *hp, losses);
     set_wino_ucache(nullptr);
     if (rc) ctx->lanes_quiesce();      // (an error in the middle of the forward: lanes may hold work)
+    ctx->carry.valid = false;          // (adopted or not: a gen_update leaves no record)
+    ctx->carry_call = ACLGAN_CARRY_OFF; ctx->carry_res = 0;
     ctx->reset_step();
     return rc;
 }
@@ -2036,6 +2187,13 @@ int aclgan_dis_update(aclgan_ctx* ctx, const float* x_a, const float* x_b, const
     rc = dis_update_impl(*ctx, x_a, x_b, z, B, H, W, *hp, losses);
     set_wino_ucache(nullptr);
     if (rc) ctx->lanes_quiesce();
+    if (ctx->carry_call == ACLGAN_CARRY_KEEP) {      // the record of what this call kept, valid for the key it ran under
+        aclgan_ctx::CarryRec& r = ctx->carry;
+        r.valid = rc == ACLGAN_OK && !ctx->carry_fail && ctx->carry_res > 0;
+        r.B = B; r.H = H; r.W = W; r.dtype = ctx->dtype; r.determ = sw(SW_DETERMINISTIC); r.x_a = x_a;
+        r.gen_epoch = ctx->gen_epoch; r.tune_epoch = tuning_epoch(); r.ws = ctx->ws; r.ws_bytes = ctx->ws_bytes; r.bytes = ctx->carry_res;
+    }
+    ctx->carry_call = ACLGAN_CARRY_OFF; ctx->carry_res = 0;
     ctx->reset_step();
     return rc;
 }
@@ -2083,6 +2241,7 @@ int aclgan_adam_step(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int ste
     ACL_REQUIRE(ctx && opt && group >= 0 && group <= 1, "bad ctx/group/opt");
     Group& g = ctx->groups[group];
     ACL_REQUIRE(g.param && g.grad && g.m && g.v, "param/grad/exp_avg/exp_avg_sq must all be bound");
+    if (group == ACLGAN_GROUP_GEN) ctx->carry_drop();      // (the generators move: kept encodings are stale)
     if (ctx->lscale) return adam_flat_scaled(g.param, g.grad, g.m, g.v, g.numel, opt, step, ctx->lscale, group, (hipStream_t)stream);
     return adam_flat(g.param, g.grad, g.m, g.v, g.numel, opt, step, (hipStream_t)stream);
 }
@@ -2091,6 +2250,7 @@ int aclgan_bind_ema(aclgan_ctx* ctx, int group, float* ema) {
     ACL_REQUIRE(ctx, "null ctx");
     ACL_REQUIRE(group == ACLGAN_GROUP_GEN, "bind_ema: only the generator group (ACLGAN_GROUP_GEN) has an averaged copy; got group %d", group);
     ctx->ema = ema;
+    ctx->carry_drop();
     if (!ema) ctx->fwd_weights = ACLGAN_WEIGHTS_LIVE;
     return ACLGAN_OK;
 }
@@ -2099,6 +2259,7 @@ int aclgan_adam_step_ema(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int
     ACL_REQUIRE(group == ACLGAN_GROUP_GEN && ctx->ema, "adam_step_ema: no averaged copy is bound for group %d (aclgan_bind_ema)", group);
     Group& g = ctx->groups[group];
     ACL_REQUIRE(g.param && g.grad && g.m && g.v, "param/grad/exp_avg/exp_avg_sq must all be bound");
+    ctx->carry_drop();
     if (ctx->lscale) return adam_flat_scaled_ema(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, ctx->lscale, group, (hipStream_t)stream);
     return adam_flat_ema(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, (hipStream_t)stream);
 }
@@ -2107,6 +2268,7 @@ int aclgan_set_forward_weights(aclgan_ctx* ctx, int which) {
     ACL_REQUIRE(which == ACLGAN_WEIGHTS_LIVE || which == ACLGAN_WEIGHTS_EMA, "set_forward_weights: %d is neither ACLGAN_WEIGHTS_LIVE nor ACLGAN_WEIGHTS_EMA", which);
     ACL_REQUIRE(which == ACLGAN_WEIGHTS_LIVE || ctx->ema, "set_forward_weights: no averaged copy is bound (aclgan_bind_ema)");
     ctx->fwd_weights = which;
+    ctx->carry_drop();
     return ACLGAN_OK;
 }
 
@@ -2114,6 +2276,7 @@ int aclgan_set_forward_weights(aclgan_ctx* ctx, int which) {
 static int fwd_begin(aclgan_ctx* ctx, void* stream) {
     ACL_REQUIRE(ctx && ctx->ws, "bind a workspace first");
     ACL_REQUIRE(ctx->groups[0].param && ctx->groups[1].param, "bind parameters first");
+    ctx->carry.valid = false; ctx->carry_arm = ACLGAN_CARRY_OFF; ctx->carry_res = 0;      // (a forward-only call may use the whole workspace)
     ctx->reset_step();
     // (peak2: the side stack's high-water mark of whatever ran before -- an update, a dry run -- is not this call's: a forward-only arena has no side stack)
     ctx->st = (hipStream_t)stream; ctx->dry = false; ctx->peak = 0; ctx->peak2 = 0; ctx->trained = -1;

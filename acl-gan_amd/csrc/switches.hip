@@ -46,6 +46,7 @@ const Switch kSwitches[SW_COUNT] = {
     {"norm_mask",         "ACLGAN_NORM_MASK",         1,  R_BOOL,  0, 0,       SETTABLE | EMPTY_UNSET, nullptr},
     {"mlp_fused",         "ACLGAN_MLP_FUSED",         1,  R_BOOL,  0, 0,       SETTABLE | EMPTY_UNSET, nullptr},
     {"fault_at",          nullptr,                    -1, R_INT,   0, 0,       SETTABLE, nullptr},
+    {"enc_reuse",         nullptr,                    1,  R_BOOL,  0, 0,       SETTABLE, nullptr},
     {"glds_tile",         "ACLGAN_GLDS_TILE",         0,  R_CLAMP, 0, INT_MAX, SETTABLE, nullptr},
     {"wino_x3",           "ACLGAN_WINO_X3",           0,  R_BOOL,  0, 0,       SETTABLE, nullptr},
     {"wino_fused",        "ACLGAN_WINO_FUSED",        1,  R_LOW4,  0, 2,       SETTABLE, nullptr},
@@ -156,10 +157,12 @@ int aclgan_tuning(const char* key, int value, int* previous) {
     return ACLGAN_OK;
 }
 // read a switch without touching it (no epoch bump, no window in which another thread sees a different value); ACLGAN_EINVAL for an unknown key.
-// key "epoch": the number of aclgan_tuning calls so far (what cached, switch-dependent results are keyed by: workspace sizes)
+// key "epoch": the number of aclgan_tuning calls so far (what cached, switch-dependent results are keyed by: workspace sizes);
+// key "enc_reuse_hits": content-encoder passes a gen_update adopted from the preceding dis_update so far (aclgan_ctx_carry_encodings)
 int aclgan_tuning_get(const char* key, long long* value) {
     ACL_REQUIRE(key && value, "aclgan_tuning_get: null argument");
     if (!strcmp(key, "epoch")) { *value = tuning_epoch(); return ACLGAN_OK; }
+    if (!strcmp(key, "enc_reuse_hits")) { *value = g_enc_reuse_hits.load(); return ACLGAN_OK; }      // read-only: encoder passes adopted so far
     const int i = find(key);
     if (i < 0) { set_error("aclgan_tuning_get: unknown key '%s'", key); return ACLGAN_EINVAL; }
     *value = sw((SwitchId)i);

@@ -122,6 +122,7 @@ class _Net:
         return OrderedDict()
 
     def load_state_dict(self, sd, strict=True):
+        self._t._carry_epoch += 1
         mine = OrderedDict(self.named_parameters())
         missing = [k for k in mine if k not in sd]
         unexpected = [k for k in sd if k not in mine and k not in self._buffers()]
@@ -371,6 +372,11 @@ class aclgan_Trainer:
         self._last_grp = None
         self._ema = None
         self._fwd_ema = False
+        # content encodings of x_a carried from a dis_update into the gen_update that follows it (_carry_state): the x_a tensor of the last
+        # eager dis_update (held, so that its storage cannot be handed to another tensor) and what must not change before gen_update adopts
+        self._carry = None
+        self._carry_epoch = 0
+        self.enc_reuse = bool(hp.get("enc_reuse", True))
         self._setup_data_parallel()
         # averaged generator (ema_decay > 0): one more flat buffer beside the generator group's, starting from this replica's weights
         # (initialised and, data-parallel, already rank 0's); the generator's Adam launch keeps it up to date (aclgan_adam_step_ema)
@@ -399,6 +405,7 @@ class aclgan_Trainer:
         return sd
 
     def load_state_dict(self, sd, strict=True):
+        self._carry_epoch += 1
         known = set()
         for n in self.NETS:
             sub = OrderedDict((k[len(n) + 1:], v) for k, v in sd.items() if k.startswith(n + "."))
@@ -543,6 +550,16 @@ class aclgan_Trainer:
         own = float(self._gscale[grp].item())
         return own if own > 0 else live
 
+    def _carry_state(self, x_a):
+        """What a gen_update may adopt the preceding dis_update's content encodings of x_a under (include/aclgan_hip.h:
+        aclgan_ctx_carry_encodings): the same x_a storage that no torch operation has written since, generator parameters and 16-bit packs
+        that no torch operation has written since (load_state_dict, a broadcast), and no weight swap or resume in between.  The library
+        checks its own side (Adam on the generators, binds, shape, dtype, workspace).  torch cannot see a loader that refills the buffer
+        behind x_a without going through a tensor operation: such a caller turns the reuse off (config key enc_reuse: false, or the library's tuning key enc_reuse 0)."""
+        g = L.GROUP_GEN
+        packs = tuple((t.data_ptr(), t._version) for t in (self._w16.get(g), self._w16t.get(g)) if t is not None)
+        return (x_a.data_ptr(), tuple(x_a.shape), x_a._version, self._param[g].data_ptr(), self._param[g]._version, packs, self._carry_epoch)
+
     def _draw_z(self, B):
         # three draws from the CPU generator, in the reference's order (trainer.py:99-101); data-parallel ranks use
         # their own generator (seed + rank) so that shards do not share noise
@@ -588,6 +605,14 @@ class aclgan_Trainer:
                 L.check(L.lib.aclgan_zero_grad(self._ctx, grp, st), "zero_grad")   # opt.zero_grad() (trainer.py:91,248)
                 if self._reducer is not None:
                     self._reducer.begin(grp)
+                # an eager dis_update keeps its content encodings of x_a; the gen_update after it adopts them if nothing changed (_carry_state)
+                kept, self._carry, carry = self._carry, None, L.CARRY_OFF
+                if self.enc_reuse and not self.hip_graph:
+                    if which == "dis":
+                        self._carry, carry = (x_a, self._carry_state(x_a)), L.CARRY_KEEP
+                    elif kept is not None and kept[0] is x_a and kept[1] == self._carry_state(x_a):
+                        carry = L.CARRY_ADOPT
+                L.check(L.lib.aclgan_ctx_carry_encodings(self._ctx, carry), "ctx_carry_encodings")
                 L.check(fn(self._ctx, L.ptr(x_a), L.ptr(x_b), L.ptr(zz), B, H, W, C.byref(hpc), L.ptr(self._losses), st), which + "_update")
             if getattr(self, "_sync_error", None) is not None:
                 raise self._sync_error
@@ -769,6 +794,7 @@ class aclgan_Trainer:
             self._select_forward_weights(prev)
 
     def _select_forward_weights(self, ema):
+        self._carry_epoch += 1
         L.check(L.lib.aclgan_set_forward_weights(self._ctx, L.WEIGHTS_EMA if ema else L.WEIGHTS_LIVE), "set_forward_weights")
         self._fwd_ema = ema
 

@@ -241,6 +241,23 @@ int aclgan_bind_workspace(aclgan_ctx* ctx, void* workspace, size_t bytes);
  * check before they enqueue anything, and the arena refuses every single request that would leave the bound range (round 5: an
  * undersized workspace fails, it never corrupts). */
 int aclgan_check_workspace(aclgan_ctx* ctx, int B, int H, int W);
+/* Content encodings of x_a carried from a dis_update into the gen_update that follows it on the same batch (NOT in the reference, which
+ * recomputes them: trainer.py:103-104 and 257-258 run the same two encoder passes on x_a, and dis_update does not touch the generators).
+ * aclgan_ctx_carry_encodings arms the NEXT update only:
+ *   ACLGAN_CARRY_KEEP   the next aclgan_dis_update leaves the tensors of encode(gen_AB, x_a) and encode(gen_BA, x_a) that a backward pass reads
+ *                       in a region at the end of the workspace (aclgan_workspace_bytes includes it while the switch enc_reuse is on);
+ *   ACLGAN_CARRY_ADOPT  the next aclgan_gen_update uses them instead of running the two passes: same results bit for bit, ~140 launches less.
+ *                       ADOPT is the caller's assertion that the CONTENTS of x_a are what that dis_update read.  The library checks the rest and
+ *                       runs the passes itself when anything differs: B, H, W, compute dtype, the x_a pointer, the bound workspace, the tuning
+ *                       switches, and that no call wrote the generators in between (aclgan_adam_step* on ACLGAN_GROUP_GEN, any bind, the
+ *                       forward-weights switch, a forward-only call).
+ * Never under stream capture, while aclgan_debug_capture_masks records, with the tuning key fault_at set, or with the tuning key
+ * enc_reuse 0 (default 1; no environment variable).  aclgan_tuning_get("enc_reuse_hits"): passes adopted so far (read-only).  aclgan_step_executed_flops and
+ * aclgan_step_algorithmic_bytes count an update as its last real call on the context ran. */
+#define ACLGAN_CARRY_OFF 0
+#define ACLGAN_CARRY_KEEP 1
+#define ACLGAN_CARRY_ADOPT 2
+int aclgan_ctx_carry_encodings(aclgan_ctx* ctx, int mode);
 /* arena for ONE forward-only call below (encode / decode / discriminator forward) on (B,*,H,W) images: what
  * test.py:55-131 and trainer.sample need -- far smaller than a training step's, and without its shape constraints
  * (any H, W the networks accept, e.g. the 256x340 a Resize(256) of a non-square photo yields) */
