@@ -62,6 +62,7 @@ GROUP_GEN, GROUP_DIS, GROUP_SN_STATE = 0, 1, 2
 EMA_COPY, EMA_BLEND = 0, 1            # ACLGAN_EMA_*
 WEIGHTS_LIVE, WEIGHTS_EMA = 0, 1      # ACLGAN_WEIGHTS_*
 CARRY_OFF, CARRY_KEEP, CARRY_ADOPT = 0, 1, 2      # ACLGAN_CARRY_*
+AUG = {"color": 1, "translation": 2, "cutout": 4}      # ACLGAN_AUG_*
 NETS = {"gen_AB": 0, "gen_BA": 1, "dis_A": 2, "dis_B": 3, "dis_2": 4}
 LOSS_NAMES = [
     "loss_gen_adv_A", "loss_gen_adv_B", "loss_gen_adv_2",
@@ -143,6 +144,10 @@ SIGNATURES = {
     "aclgan_tuning_get": (ci, [C.c_char_p, C.POINTER(C.c_longlong)]),
     "aclgan_check_workspace": (ci, [vp, ci, ci, ci]),
     "aclgan_ctx_carry_encodings": (ci, [vp, ci]),
+    "aclgan_ctx_set_augment": (ci, [vp, ci, vp, ci]),
+    "aclgan_diffaugment_scratch_bytes": (sz, [ci, ci, ci, ci]),
+    "aclgan_diffaugment_fwd": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "aclgan_diffaugment_bwd": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp]),
     "aclgan_conv2d_fwd16s_stats_chunk": (ci, [C.POINTER(ConvDesc)]),
     "aclgan_conv2d_fwd16s_stats": (ci, [C.POINTER(ConvDesc), ci, vp, vp, vp, vp, ci, vp, vp]),
     "aclgan_conv2d_dgrad16s_scratch_bytes": (sz, [C.POINTER(ConvDesc)]),

@@ -224,6 +224,11 @@ int positive_mask(const void* y, int yst, unsigned char* dst, int64_t n, hipStre
 int positive_mask_diff(const float* a, int ca, const float* b, int cb, unsigned char* dst, int64_t npix, hipStream_t st);      // dst[i] = y[i] > 0 (diagnostics)
 int avgpool3s2_fwd(int B, int H, int W, int C, const float* x, float* y, hipStream_t st);
 int avgpool3s2_bwd(int B, int H, int W, int C, const float* dy, float* dx, int accumulate, hipStream_t st);
+// DiffAugment of a discriminator input (augment.hip): colour / translation / cutout by the rows of params [N][8]; scratch
+// (diffaugment_scratch_bytes: the ordered partial sums of the colour operation) may be null when policy has no colour bit
+size_t diffaugment_scratch_bytes(int N, int H, int W, int C);
+int diffaugment_fwd(int N, int H, int W, int C, int policy, const float* x, const float* params, float* y, void* scratch, hipStream_t st);
+int diffaugment_bwd(int N, int H, int W, int C, int policy, const float* dy, const float* params, float* dx, int accumulate, void* scratch, hipStream_t st);
 int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, hipStream_t st);
 // the same launch with the exponential moving average of p as one more stream (mode: ACLGAN_EMA_COPY / ACLGAN_EMA_BLEND); p, m, v as adam_flat
 int adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode, hipStream_t st);

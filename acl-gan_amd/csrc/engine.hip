@@ -236,6 +236,12 @@ struct aclgan_ctx {
     };
     CarryRec carry;
     long long gen_epoch = 0;
+    // ---- Differentiable augmentation of the discriminator inputs (aclgan_ctx_set_augment; augment.hip).  aug_policy 0:
+    // off -- dis_lsgan builds exactly the passes it built before the feature existed.  Otherwise every dis_lsgan call augments its input by the
+    // rows [row0, row0 + batch) of aug_params (device memory, read stream-ordered) into a fresh activation and runs the discriminator on that.
+    int aug_policy = 0;
+    const float* aug_params = nullptr;
+    int aug_rows = 0;
     int carry_arm = ACLGAN_CARRY_OFF;            // what the caller armed for the next update
     int carry_call = ACLGAN_CARRY_OFF;           // mode of the update being built (dry runs: the mode being sized)
     int carry_mode = ACLGAN_CARRY_OFF;           // mode of the pass being built: carry_call inside the two carried passes, OFF elsewhere
@@ -1406,8 +1412,53 @@ static int dis_forward(aclgan_ctx& c, int net, bool train, Act* x, std::vector<A
 // linear in the reported losses.  Round 5: ONE launch for all scales and segments of the call (networks.py:64-67,81-83,96-98
 // loop over the scales in Python), the terms added to their slots in the order of the former per-term launches.
 struct LsSeg { float target, weight, gscale; float* slot; };
-static int dis_lsgan(aclgan_ctx& c, int net, bool train, Act* x, int nb, const std::vector<LsSeg>& segs, int lane_a = -1, int lane_b = -1) {
+// DiffAugment of a discriminator input (augment.hip) on the current lane: y = T(x) by the parameter rows [row0, row0 + x->B); the gradient
+// of y goes back into x's gradient buffer (overwrite or accumulate, as every other consumer of x does)
+static int augment(aclgan_ctx& c, int net, Act* x, int row0, Act** out) {
+    PassScope pass(c, net, "augment");
+    CHK(c.need(x));
+    if (x->dt != 0) { set_error("augment: the discriminator inputs are fp32 tensors"); return ACLGAN_EINVAL; }
+    Act* y = c.new_act(x->B, x->H, x->W, x->C, x->need_grad);
+    NEED(y->d); if (y->need_grad) NEED(y->g);
+    const int policy = c.aug_policy;
+    const size_t sb = (policy & ACLGAN_AUG_COLOR) ? diffaugment_scratch_bytes(x->B, x->H, x->W, x->C) : 0;
+    const float* rows = c.aug_params ? c.aug_params + (size_t)row0 * 8 : nullptr;      // (dry runs have none)
+    {
+        const size_t mark = c.top;
+        void* scr = nullptr;
+        if (sb) { scr = c.alloc(sb); NEED(scr); }
+        RUN(diffaugment_fwd(x->B, x->H, x->W, x->C, policy, x->d, rows, y->d, scr, c.st));
+        c.top = mark;
+    }
+    c.wrote(y);
+    c.count(4.0 * 2.0 * (double)x->numel() * (x->need_grad ? 2.0 : 1.0));
+    *out = y;
+    if (!x->need_grad) return ACLGAN_OK;
+    aclgan_ctx* cp = &c;
+    c.push([=]() -> int {
+        aclgan_ctx& c = *cp;
+        if (!y->gw) return ACLGAN_OK;
+        CHK(c.acq(y)); CHK(c.acq(x));
+        if (y->gdt != 0 || x->gdt != 0) { set_error("augment: the gradients of the discriminator inputs are fp32 tensors"); return ACLGAN_EINVAL; }
+        const size_t mark = c.top;
+        void* scr = nullptr;
+        if (sb) { scr = c.alloc(sb); NEED(scr); }
+        RUN(diffaugment_bwd(x->B, x->H, x->W, x->C, policy, y->g, rows, x->g, x->gw ? 1 : 0, scr, c.st));
+        mark_written(x);
+        c.top = mark;
+        return ACLGAN_OK;
+    });
+    return ACLGAN_OK;
+}
+
+// row0: the first row of the augmentation parameters that belongs to x (aclgan_ctx_set_augment; ignored while the policy is 0)
+static int dis_lsgan(aclgan_ctx& c, int net, bool train, Act* x, int nb, int row0, const std::vector<LsSeg>& segs, int lane_a = -1, int lane_b = -1) {
     std::vector<Act*> outs;
+    if (c.aug_policy) {
+        if (lane_a >= 0) CHK(c.set_lane(lane_a));
+        CHK(augment(c, net, x, row0, &x));
+        CHK(c.mark());
+    }
     CHK(dis_forward(c, net, train, x, &outs, lane_a, lane_b));
     std::vector<LsganTerm> terms;
     for (Act* o : outs) {
@@ -1678,18 +1729,18 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     PASS(decode(c, AB, true, c4, s4, &rB4)); CHK(zero_grad_of(c, rB4));   // trainer.py:114
     // adversarial terms (trainer.py:136-139); discriminators frozen.  dis_B only needs x_B_fake: it is enqueued first; each pass runs its
     // full-resolution scale on one lane and the coarser scales on the other
-    PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, false, xB, B, {{1.f, 1.f, hp.gan_w, L + ACLGAN_L_GEN_ADV_B}}, L1, LS));
+    PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, false, xB, B, 2 * B, {{1.f, 1.f, hp.gan_w, L + ACLGAN_L_GEN_ADV_B}}, L1, LS));
     if (c.dis_norm != ACLGAN_NORM_SN) {
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, jA, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}, {1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, jP, B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2},     // networks.py:98: pair_A1 -> 1
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, jA, B, 0, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}, {1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, jP, B, 3 * B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2},     // networks.py:98: pair_A1 -> 1
                                                             {0.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));  //                 pair_A2 -> 0
     } else {
         // spectral norm: every reference call advances u, so each is a pass of its own, in the reference's order (trainer.py:136-139);
         // one discriminator's calls stay on one lane pair (its power iterations form a chain)
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, vA1, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, vA2, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, vP1, B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, vP2, B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, vA1, B, 0, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, false, vA2, B, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_GEN_ADV_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, vP1, B, 3 * B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, false, vP2, B, 4 * B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_GEN_ADV_2}}, L1, LS));
     }
     CHK(c.lanes_join());                                              // the loss kernels below read all of it, on lane 0
     // focus losses (trainer.py:145-161)
@@ -1807,27 +1858,27 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     const bool sn = c.dis_norm == ACLGAN_NORM_SN;
     // spectral norm: one pass per reference call, in the reference's order (calc_dis_loss: fake, then real; trainer.py:283-286), and the
     // real branch of loss_dis_A twice (each call has its own sigma)
-    if (!sn) PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, jB, B, {{0.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}, {1.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
+    if (!sn) PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, jB, B, 3 * B, {{0.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}, {1.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
     else {
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, c.new_view(jB, 0, B), B, {{0.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, c.new_view(jB, B, B), B, {{1.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, c.new_view(jB, 0, B), B, 3 * B, {{0.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_B, true, c.new_view(jB, B, B), B, 4 * B, {{1.f, 1.f, hp.gan_w, L + ACLGAN_L_DIS_B}}, L1, L2));
     }
     CHK(c.set_lane(L0));
     PASS(content_encode(c, BA, false, xB, &c3));
     PASS(decode(c, BA, false, c3, z3, &dA24));
     PASS(blend(c, dA24, xB, xa, &xA2, &pA2, c.new_view(jA, B, B), c.new_view(jP, B, B)));
     if (!sn) {
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, jA, B, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}, {0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A},
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, jA, B, 0, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}, {0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A},
                                                            {1.f, 1.0f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));   // the real branch occurs twice x 0.5
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, jP, B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}, {1.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, jP, B, 5 * B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}, {1.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
     } else {
         Act* vx = c.new_view(jA, 2 * B, B);
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, c.new_view(jA, 0, B), B, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, vx, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, c.new_view(jA, B, B), B, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, vx, B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, c.new_view(jP, 0, B), B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
-        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, c.new_view(jP, B, B), B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, c.new_view(jA, 0, B), B, 0, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, vx, B, 2 * B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, c.new_view(jA, B, B), B, B, {{0.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_A, true, vx, B, 2 * B, {{1.f, 0.5f, hp.gan_w, L + ACLGAN_L_DIS_A}}, L0, L2));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, c.new_view(jP, 0, B), B, 5 * B, {{0.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
+        PASS(dis_lsgan(c, ACLGAN_NET_DIS_2, true, c.new_view(jP, B, B), B, 6 * B, {{1.f, 1.f, hp.gan_cw, L + ACLGAN_L_DIS_2}}, L1, LS));
     }
     CHK(c.lanes_join());
     if (!c.dry) {
@@ -2110,12 +2161,30 @@ int aclgan_ctx_carry_encodings(aclgan_ctx* ctx, int mode) {
     return ACLGAN_OK;
 }
 
+int aclgan_ctx_set_augment(aclgan_ctx* ctx, int policy, const float* params, int rows) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(policy >= 0 && policy <= (ACLGAN_AUG_COLOR | ACLGAN_AUG_TRANSLATION | ACLGAN_AUG_CUTOUT),
+                "set_augment: policy %d is neither 0 nor a combination of ACLGAN_AUG_COLOR | ACLGAN_AUG_TRANSLATION | ACLGAN_AUG_CUTOUT", policy);
+    ACL_REQUIRE(rows >= 0, "set_augment: rows = %d", rows);
+    ctx->aug_policy = policy;
+    ctx->aug_params = policy ? params : nullptr;
+    ctx->aug_rows = policy ? rows : 0;
+    return ACLGAN_OK;
+}
+
 static int step_common(aclgan_ctx* ctx, const float* x_a, const float* x_b, const float* z, const aclgan_hparams* hp, float* losses, void* stream, int group_trained,
                        int B, int H, int W) {
     ACL_REQUIRE(ctx && x_a && x_b && z && hp && losses, "null argument");
     ACL_REQUIRE(ctx->ws, "bind a workspace first (aclgan_workspace_bytes / aclgan_bind_workspace)");
     ACL_REQUIRE(ctx->groups[0].param && ctx->groups[1].param, "bind parameters first");
     ACL_REQUIRE(ctx->groups[group_trained].grad, "gradient buffer of the trained group is not bound");
+    if (ctx->aug_policy) {      // (refused here, before anything is enqueued)
+        const int want = (group_trained == 0 ? 5 : 7) * B;
+        ACL_REQUIRE(ctx->aug_params, "%s with augmentation policy %d needs the parameter rows: aclgan_ctx_set_augment was given params = NULL",
+                    group_trained == 0 ? "gen_update" : "dis_update", ctx->aug_policy);
+        ACL_REQUIRE(ctx->aug_rows == want, "%s at B = %d reads %d augmentation rows (%d B), aclgan_ctx_set_augment was given %d",
+                    group_trained == 0 ? "gen_update" : "dis_update", B, want, group_trained == 0 ? 5 : 7, ctx->aug_rows);
+    }
     // the bound workspace against this update's need (a dry run, cached per shape / dtype / switch setting): an undersized workspace is
     // refused here, before anything is enqueued (the allocator checks every request as well)
     // carried encodings: what the caller armed holds for this call only.  dis_update keeps when armed; gen_update adopts when armed and the
@@ -2140,7 +2209,7 @@ static int step_common(aclgan_ctx* ctx, const float* x_a, const float* x_b, cons
     // refused here, before anything is enqueued (the allocator checks every request as well)
     if (check_shape(*ctx, B, H, W) == ACLGAN_OK) {
         for (;;) {
-            const aclgan_ctx::NeedKey key{group_trained, B, H, W, ctx->dtype, tuning_epoch(), sw(SW_DETERMINISTIC), (ctx->bucket_elems > 0 ? 1 : 0) | (carry << 1)};
+            const aclgan_ctx::NeedKey key{group_trained, B, H, W, ctx->dtype, tuning_epoch(), sw(SW_DETERMINISTIC), (ctx->bucket_elems > 0 ? 1 : 0) | (carry << 1) | (ctx->aug_policy << 3)};
             auto it = ctx->need_cache.find(key);
             if (it == ctx->need_cache.end()) {
                 size_t need = 0;

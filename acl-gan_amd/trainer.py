@@ -20,7 +20,8 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "dis_norm_from_config", "ema_from_config", "hparams_from_config"]
+__all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "augment_from_config", "dis_norm_from_config", "draw_augment_params",
+           "ema_from_config", "hparams_from_config"]
 
 DIS_NORMS = ("none", "sn")    # dis.norm values the library implements (sn: SpectralNorm, networks.py:360-361,538-600)
 
@@ -62,6 +63,58 @@ def ema_from_config(hp):
     if display and not decay > 0:
         raise L.AclganError("ema_display: true needs ema_decay > 0 (there is no averaged generator to sample from)")
     return float(decay), start, display
+
+
+def augment_from_config(hp):
+    """dis_augment (not in the reference): a comma-separated subset of color,translation,cutout -- the differentiable augmentation every
+    discriminator input of both updates goes through (Zhao et al. 2020) -- as the library's ACLGAN_AUG_* policy bits.  Default "" = 0 = off:
+    no buffer, no extra library call, the launches of a run without the key."""
+    v = hp.get("dis_augment", "")
+    if not isinstance(v, str):
+        raise L.AclganError("dis_augment=%r: expected a string, a comma-separated subset of %s" % (v, ",".join(L.AUG)))
+    policy = 0
+    if v.strip() == "":
+        return policy
+    for name in (t.strip() for t in v.split(",")):
+        if name not in L.AUG or policy & L.AUG[name]:
+            raise L.AclganError("dis_augment=%r: %r is %s (expected a comma-separated subset of %s)"
+                                % (v, name, "named twice" if name in L.AUG else "unknown", ",".join(L.AUG)))
+        policy |= L.AUG[name]
+    return policy
+
+
+AUG_SEED_OFFSET = 0x0A06            # the augmentation generator's seed = torch.initial_seed() + rank + this
+
+
+def draw_augment_params(policy, rows, H, W, generator=None):
+    """(rows, 8) fp32 CPU tensor of augmentation parameters (b, s, c, tx, ty, cx, cy, 0), one row per discriminator input image, with
+    DiffAugment's distributions (include/aclgan_hip.h: aclgan_diffaugment_fwd for what the columns do):
+      color        b = U[0,1) - 0.5 (brightness), s = 2 U[0,1) (saturation), c = U[0,1) + 0.5 (contrast)
+      translation  tx uniform on the integers [-Sx, Sx], Sx = int(W/8 + 0.5); ty likewise with H
+      cutout       a (ch, cw) = ((H+1)//2, (W+1)//2) rectangle; oy uniform on the integers [0, H + (1 - ch % 2)), cy = oy - ch//2; cx likewise
+    The columns of an operation that policy leaves out hold its neutral values: 0, 1, 1; 0, 0; a rectangle outside the frame (cx = W, cy = H).
+    Draw order: b, s, c, tx, ty, cx, cy, each for all rows at once and only for the operations that are on."""
+    if not (isinstance(policy, int) and 0 <= policy <= 7) or rows < 0 or H < 1 or W < 1:
+        raise L.AclganError("draw_augment_params: bad arguments (policy %r, rows %r, H %r, W %r)" % (policy, rows, H, W))
+    p = torch.zeros(rows, 8, dtype=torch.float32)
+    p[:, 1] = 1.0
+    p[:, 2] = 1.0
+    p[:, 5] = float(W)
+    p[:, 6] = float(H)
+    g = generator
+    if policy & L.AUG["color"]:
+        p[:, 0] = torch.rand(rows, generator=g) - 0.5
+        p[:, 1] = torch.rand(rows, generator=g) * 2.0
+        p[:, 2] = torch.rand(rows, generator=g) + 0.5
+    if policy & L.AUG["translation"]:
+        sx, sy = int(W / 8 + 0.5), int(H / 8 + 0.5)
+        p[:, 3] = torch.randint(-sx, sx + 1, (rows,), generator=g).float()
+        p[:, 4] = torch.randint(-sy, sy + 1, (rows,), generator=g).float()
+    if policy & L.AUG["cutout"]:
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        p[:, 5] = (torch.randint(0, W + (1 - cw % 2), (rows,), generator=g) - cw // 2).float()
+        p[:, 6] = (torch.randint(0, H + (1 - ch % 2), (rows,), generator=g) - ch // 2).float()
+    return p
 
 
 def hparams_from_config(hp):
@@ -260,6 +313,7 @@ class aclgan_Trainer:
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.arch = arch_from_config(hp)
         self._ema_decay, self._ema_start, self.ema_display = ema_from_config(hp)
+        self.augment = augment_from_config(hp)      # ACLGAN_AUG_* bits of dis_augment (0: off)
         # compute dtype of the heavy convolutions (not in the reference, which is fp32 only): "fp32" | "bf16" | "fp16"
         self.compute_dtype = str(compute_dtype or hp.get("compute_dtype", "fp32"))
         if self.compute_dtype not in L.DTYPE:
@@ -281,6 +335,13 @@ class aclgan_Trainer:
         self._ctx = C.c_void_p()
         L.check(L.lib.aclgan_ctx_create_dis_norm(C.byref(self.arch), dis_norm_from_config(hp), C.byref(self._ctx)), "ctx_create")
         L.check(L.lib.aclgan_set_compute_dtype(self._ctx, L.DTYPE[self.compute_dtype]), "set_compute_dtype")
+        # dis_augment: the policy goes on the context before the first workspace query (the augmented tensors live in the arena); the rows
+        # of an update are bound just before it (_bind_augment).  They come from a CPU generator of their own (seed: initial_seed() + rank +
+        # AUG_SEED_OFFSET), so the z stream of a run is the same with and without augmentation; its state is not part of a checkpoint.
+        self._auggen = None
+        self._aug_dev = {}
+        if self.augment:
+            L.check(L.lib.aclgan_ctx_set_augment(self._ctx, self.augment, None, 0), "ctx_set_augment")
         # the lane scheduler's streams first, before anything else of this process creates one (the rank-0 broadcast below initialises the process
         # group's communicator and its stream): HIP binds streams to hardware queues in creation order (include/aclgan_hip.h, aclgan_warm_streams)
         if os.environ.get("ACLGAN_WARM_STREAMS", "1") not in ("", "0"):
@@ -576,18 +637,44 @@ class aclgan_Trainer:
         for i in range(lo, hi):
             setattr(self, L.LOSS_NAMES[i], vals[i - lo])
 
-    def _update(self, which, x_a, x_b, hp, z):
+    def _draw_augment(self, which, B, H, W):
+        """a fresh draw of this update's augmentation rows from the trainer's own CPU generator"""
+        if self._auggen is None:
+            import torch.distributed as dist
+            rank = dist.get_rank() if self._dist_world() else 0
+            self._auggen = torch.Generator().manual_seed((torch.initial_seed() + rank + AUG_SEED_OFFSET) % (1 << 63))
+        return draw_augment_params(self.augment, (5 if which == "gen" else 7) * B, H, W, self._auggen)
+
+    def _bind_augment(self, which, aug):
+        """This update's augmentation rows into the persistent device tensor of (update, row count) the context reads them from
+        (persistent: a replayed graph reads the address it was captured with).  Returns that tensor."""
+        if not (isinstance(aug, torch.Tensor) and aug.dim() == 2 and aug.shape[1] == 8):
+            raise L.AclganError("aug: expected a (rows, 8) tensor of augmentation parameters (draw_augment_params)")
+        key = (which, aug.shape[0])
+        dev = self._aug_dev.get(key)
+        if dev is None:
+            dev = self._aug_dev[key] = torch.zeros(aug.shape[0], 8, dtype=torch.float32, device=self.device)
+        dev.copy_(aug.to(torch.float32))
+        L.check(L.lib.aclgan_ctx_set_augment(self._ctx, self.augment, L.ptr(dev), dev.shape[0]), "ctx_set_augment")
+        return dev
+
+    def _update(self, which, x_a, x_b, hp, z, aug=None):
         grp = L.GROUP_GEN if which == "gen" else L.GROUP_DIS
         x_a = x_a.to(self.device, torch.float32).contiguous()
         x_b = x_b.to(self.device, torch.float32).contiguous()
         B, Cc, H, W = x_a.shape
         if x_b.shape != x_a.shape or Cc != 3:
             raise L.AclganError("x_a / x_b must both be (B,3,H,W); got %s and %s" % (tuple(x_a.shape), tuple(x_b.shape)))
+        if aug is not None and not self.augment:
+            raise L.AclganError("aug given, but this trainer was built without dis_augment")
+        if self.augment and aug is None:      # (host work: before the copies below, which wait for the device)
+            aug = self._draw_augment(which, B, H, W)
         if z is None:
             z = self._draw_z(B)
         zz = torch.stack([t.reshape(B, self.style_dim).to(torch.float32) for t in z]).to(self.device).contiguous()
         hpc = hparams_from_config(hp)
         with torch.cuda.device(self.device):
+            aug_dev = self._bind_augment(which, aug) if self.augment else None
             det_now = bool(L.lib.aclgan_get_deterministic())
             if det_now != self.deterministic:      # the process-wide mode changed under us: scratch sizes depend on it
                 self.deterministic = det_now
@@ -599,7 +686,7 @@ class aclgan_Trainer:
                 self._gscale[grp:grp + 1].copy_(self._lscale[0:1])
                 self._last_grp = grp
             fn = L.lib.aclgan_gen_update if which == "gen" else L.lib.aclgan_dis_update
-            if self.hip_graph and self._reducer is None and self._run_graph(which, grp, fn, x_a, x_b, zz, B, H, W, hpc):
+            if self.hip_graph and self._reducer is None and self._run_graph(which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev):
                 pass        # zero_grad + update replayed from the captured graph
             else:
                 L.check(L.lib.aclgan_zero_grad(self._ctx, grp, st), "zero_grad")   # opt.zero_grad() (trainer.py:91,248)
@@ -631,10 +718,12 @@ class aclgan_Trainer:
             self._publish_losses(12, 16)
 
     # ---- HIP-graph replay of an update (opt-in, see __init__) ----
-    def _run_graph(self, which, grp, fn, x_a, x_b, zz, B, H, W, hpc):
+    def _run_graph(self, which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev=None):
         """True: the update ran as a graph replay.  False: run it eagerly (first call of a new key -- it also performs the
         library's one-time initialisation outside any capture -- or capture is unavailable)."""
         key = (B, H, W, bytes(hpc), self._ws.data_ptr(), self._ws.numel(), self.compute_dtype, self.deterministic)
+        if self.augment:      # (the captured kernels read the policy and the address of the rows; the rows themselves are refilled before every replay)
+            key += (self.augment, aug_dev.data_ptr(), aug_dev.shape[0])
         ent = self._graphs.get(which)
         if ent is None or ent["key"] != key:
             self._graphs[which] = {"key": key, "graph": None}
@@ -744,11 +833,13 @@ class aclgan_Trainer:
         return v
 
     # ---- the hot path (trainer.py:90-170, 247-293) ----
-    def gen_update(self, x_a, x_b, hyperparameters, z=None):
-        self._update("gen", x_a, x_b, hyperparameters, z)
+    def gen_update(self, x_a, x_b, hyperparameters, z=None, aug=None):
+        """aug (tests): this update's (5 B, 8) augmentation rows instead of a draw (dis_augment; include/aclgan_hip.h: aclgan_ctx_set_augment)"""
+        self._update("gen", x_a, x_b, hyperparameters, z, aug)
 
-    def dis_update(self, x_a, x_b, hyperparameters, z=None):
-        self._update("dis", x_a, x_b, hyperparameters, z)
+    def dis_update(self, x_a, x_b, hyperparameters, z=None, aug=None):
+        """aug (tests): this update's (7 B, 8) augmentation rows instead of a draw"""
+        self._update("dis", x_a, x_b, hyperparameters, z, aug)
 
     def update_learning_rate(self):   # trainer.py:295-299, called every iteration (train.py:101)
         self._sched_calls += 1

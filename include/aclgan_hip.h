@@ -258,6 +258,24 @@ int aclgan_check_workspace(aclgan_ctx* ctx, int B, int H, int W);
 #define ACLGAN_CARRY_KEEP 1
 #define ACLGAN_CARRY_ADOPT 2
 int aclgan_ctx_carry_encodings(aclgan_ctx* ctx, int mode);
+/* Differentiable augmentation of the discriminator inputs (NOT in the reference; Zhao et al. 2020, "DiffAugment").
+ * policy: 0 (a context's default: off, the launches, buffers and bits of a context that never heard of it) or any combination of the
+ * ACLGAN_AUG_* bits.  With a non-zero policy every discriminator pass of aclgan_gen_update / aclgan_dis_update first augments its input
+ * (aclgan_diffaugment_fwd below) into a fresh tensor -- all scales of the discriminator see the augmented image -- and the generators'
+ * gradient flows back through aclgan_diffaugment_bwd.  Nothing else of an update changes: the generators, the identity and focus losses,
+ * the carried encodings, the gradient buckets; the forward-only entry points never augment.
+ * params: DEVICE memory, rows x 8 floats (b, s, c, tx, ty, cx, cy, 0), read stream-ordered by the updates that follow (the pointer is kept,
+ * not the contents: refill it between updates, also under a captured graph).  Rows in joint-batch order, B per block:
+ *   aclgan_gen_update  rows = 5 B:  x_A_fake, x_A2_fake, x_B_fake, pair_A1, pair_A2
+ *   aclgan_dis_update  rows = 7 B:  x_A_fake, x_A2_fake, x_a, x_B_fake, x_b, pair_A1, pair_A2
+ * The real x_a batch of dis_A is augmented ONCE (one block) where the reference calls dis_A(x_a) twice: both calls see the same augmented
+ * images (this library's definition; under dis.norm sn the block serves both passes).  An update whose rows is not 5 B / 7 B, or whose
+ * params is NULL, returns ACLGAN_EINVAL and launches nothing.  NULL / 0 are fine for the launch-free queries (aclgan_workspace_bytes,
+ * aclgan_step_algorithmic_bytes, aclgan_step_executed_flops), which account for the augmented tensors and the extra launches. */
+#define ACLGAN_AUG_COLOR 1
+#define ACLGAN_AUG_TRANSLATION 2
+#define ACLGAN_AUG_CUTOUT 4
+int aclgan_ctx_set_augment(aclgan_ctx* ctx, int policy, const float* params, int rows);
 /* arena for ONE forward-only call below (encode / decode / discriminator forward) on (B,*,H,W) images: what
  * test.py:55-131 and trainer.sample need -- far smaller than a training step's, and without its shape constraints
  * (any H, W the networks accept, e.g. the 256x340 a Resize(256) of a non-square photo yields) */
@@ -523,6 +541,22 @@ size_t aclgan_norm_scratch_bytes(int B, int HW, int C);
 int aclgan_avgpool3s2_fwd(int B, int H, int W, int C, const float* x, float* y, void* stream);
 int aclgan_avgpool3s2_bwd(int B, int H, int W, int C, const float* dy, float* dx, int accumulate,
                           void* stream);
+
+/* DiffAugment (csrc/augment.hip): x [N][H][W][C] NHWC fp32, C = 3 (an image) or 6 (a pair of images: two 3-channel groups that share one
+ * parameter row); params [N][8] fp32 on the device = (b, s, c, tx, ty, cx, cy, 0), tx / ty / cx / cy integers stored as floats; policy =
+ * ACLGAN_AUG_COLOR | ACLGAN_AUG_TRANSLATION | ACLGAN_AUG_CUTOUT (1..7); the columns of a clear bit are not read.  In this order:
+ *   colour       u = x + b;  pm = mean_c(u) per pixel;  v = (u - pm) s + pm;  m = mean_{c,h,w}(v) of the group;  w = (v - m) c + m
+ *   translation  y[i][j] = w[i + ty][j + tx] inside the frame, else 0
+ *   cutout       y[i][j] = 0 for cy <= i < cy + (H+1)/2 and cx <= j < cx + (W+1)/2
+ * bwd is the exact adjoint: dx (+)= ... of dy (accumulate != 0: +=).  The operator is linear, so a loss scale passes through.
+ * Any H, W.  The two per-(sample, group) means are added from partial sums in a fixed order (scratch: aclgan_diffaugment_scratch_bytes;
+ * may be NULL when the colour bit is clear): forward and backward give the same bits run to run.  With the colour bit clear the output
+ * holds copies of input bits (identical to x when tx = ty = 0 and the rectangle lies outside the frame).  x and y must not alias.
+ * ACLGAN_EINVAL for C outside {3, 6}, a policy outside 1..7 or a null buffer. */
+size_t aclgan_diffaugment_scratch_bytes(int N, int H, int W, int C);
+int aclgan_diffaugment_fwd(int N, int H, int W, int C, int policy, const float* x, const float* params, float* y, void* scratch, void* stream);
+int aclgan_diffaugment_bwd(int N, int H, int W, int C, int policy, const float* dy, const float* params, float* dx, int accumulate,
+                           void* scratch, void* stream);
 
 /* LinearBlock / MLP layer (networks.py:373-418, 280-292) and the style head's 1x1 conv on a pooled vector (networks.py:223):
  * y[b][o] = act(sum_i x[b][i] W[o][i] + bias[o]).  bwd: dy is modified in place by the activation backward; dx is
