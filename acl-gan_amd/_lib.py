@@ -148,6 +148,8 @@ SIGNATURES = {
     "aclgan_diffaugment_scratch_bytes": (sz, [ci, ci, ci, ci]),
     "aclgan_diffaugment_fwd": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "aclgan_diffaugment_bwd": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp]),
+    "aclgan_dis_r1_scratch_bytes": (sz, [vp, ci, ci, ci, ci]),
+    "aclgan_dis_r1": (ci, [vp, ci, vp, ci, ci, ci, cf, vp, vp, vp, vp]),
     "aclgan_conv2d_fwd16s_stats_chunk": (ci, [C.POINTER(ConvDesc)]),
     "aclgan_conv2d_fwd16s_stats": (ci, [C.POINTER(ConvDesc), ci, vp, vp, vp, vp, ci, vp, vp]),
     "aclgan_conv2d_dgrad16s_scratch_bytes": (sz, [C.POINTER(ConvDesc)]),

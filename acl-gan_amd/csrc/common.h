@@ -229,6 +229,17 @@ int avgpool3s2_bwd(int B, int H, int W, int C, const float* dy, float* dx, int a
 size_t diffaugment_scratch_bytes(int N, int H, int W, int C);
 int diffaugment_fwd(int N, int H, int W, int C, int policy, const float* x, const float* params, float* y, void* scratch, hipStream_t st);
 int diffaugment_bwd(int N, int H, int W, int C, int policy, const float* dy, const float* params, float* dx, int accumulate, void* scratch, hipStream_t st);
+// R1 gradient penalty (r1.hip).  DisView: what the pass reads of a context -- one un-normalised discriminator's tensors inside the bound
+// DIS group (layer l < n_layer: the 4x4 stride-2 convolutions, l == n_layer: the 1x1 head; index s * (n_layer + 1) + l) and the bound
+// loss-scale state.  Filled by dis_view (engine.hip, where the context is defined): ACLGAN_EINVAL for a null context or a net that is no
+// discriminator, ACLGAN_EUNSUPPORTED under spectral normalisation; w / dw are null while the group's buffers are not bound.
+struct DisView {
+    int cin = 0, dim = 0, n_layer = 0, num_scales = 0;
+    const float* lscale = nullptr;
+    const float* w[64]; const float* b[64]; float* dw[64];
+};
+const int DIS_VIEW_MAX = 64;
+int dis_view(const aclgan_ctx* ctx, int net, DisView* v);
 int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, hipStream_t st);
 // the same launch with the exponential moving average of p as one more stream (mode: ACLGAN_EMA_COPY / ACLGAN_EMA_BLEND); p, m, v as adam_flat
 int adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode, hipStream_t st);

@@ -2418,3 +2418,29 @@ int aclgan_dis_forward(aclgan_ctx* ctx, int net, const float* x, int B, int H, i
 }
 
 }  // extern "C"
+
+// the R1 pass (r1.hip) runs beside the updates, on buffers of its own: all it needs of a context is where one discriminator's tensors lie
+int aclgan::dis_view(const aclgan_ctx* ctx, int net, DisView* v) {
+    ACL_REQUIRE(ctx && v, "dis_r1: null ctx");
+    ACL_REQUIRE(net >= ACLGAN_NET_DIS_A && net <= ACLGAN_NET_DIS_2, "dis_r1: net %d is no discriminator (ACLGAN_NET_DIS_A / _DIS_B / _DIS_2)", net);
+    if (ctx->dis_norm == ACLGAN_NORM_SN) {
+        set_error("dis_r1: the penalty under dis.norm sn (folding through sigma, the power-iteration state) is not implemented");
+        return ACLGAN_EUNSUPPORTED;
+    }
+    const aclgan_arch& a = ctx->arch;
+    ACL_REQUIRE(a.dis_num_scales * (a.dis_n_layer + 1) <= DIS_VIEW_MAX, "dis_r1: more than %d discriminator layers", DIS_VIEW_MAX);
+    v->cin = net == ACLGAN_NET_DIS_2 ? a.input_dim_b : a.input_dim_a;
+    v->dim = a.dis_dim; v->n_layer = a.dis_n_layer; v->num_scales = a.dis_num_scales;
+    v->lscale = ctx->lscale;
+    char buf[160];
+    for (int s = 0; s < a.dis_num_scales; ++s)
+        for (int l = 0; l <= a.dis_n_layer; ++l) {
+            snprintf(buf, sizeof buf, l < a.dis_n_layer ? "cnns.%d.%d.conv" : "cnns.%d.%d", s, l);
+            const int i = s * (a.dis_n_layer + 1) + l;
+            // (null while the group is not bound; the 16-bit packs of a PW are not read: the pass is fp32)
+            v->w[i] = ctx->param(ACLGAN_GROUP_DIS, net, std::string(buf) + ".weight");
+            v->b[i] = ctx->param(ACLGAN_GROUP_DIS, net, std::string(buf) + ".bias");
+            v->dw[i] = ctx->gradp(ACLGAN_GROUP_DIS, net, std::string(buf) + ".weight");
+        }
+    return ACLGAN_OK;
+}

@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 
 __all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "augment_from_config", "dis_norm_from_config", "draw_augment_params",
-           "ema_from_config", "hparams_from_config"]
+           "ema_from_config", "hparams_from_config", "r1_from_config"]
 
 DIS_NORMS = ("none", "sn")    # dis.norm values the library implements (sn: SpectralNorm, networks.py:360-361,538-600)
 
@@ -81,6 +81,28 @@ def augment_from_config(hp):
                                 % (v, name, "named twice" if name in L.AUG else "unknown", ",".join(L.AUG)))
         policy |= L.AUG[name]
     return policy
+
+
+def r1_from_config(hp):
+    """The R1 gradient penalty's keys (not in the reference; Mescheder et al. 2018, in StyleGAN2's lazy form) as (gamma, every):
+    r1_gamma  float >= 0, default 0 = off: no buffer, no library call, the launches and bits of a run without the keys;
+    r1_every  int >= 1, default 16: the pass runs on every r1_every-th discriminator update, with gamma * r1_every.
+    The penalty gamma/2 E||grad_x D(x)||^2 is taken on the real batches: dis_A on x_a, dis_B on x_b (dis_2 never sees a real image).
+    Refused with r1_gamma > 0: dis.norm sn (the pass does not fold through sigma) and dis_augment (the pass does not wrap the augmentation)."""
+    gamma, every = hp.get("r1_gamma", 0), hp.get("r1_every", 16)
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not (0 <= gamma and math.isfinite(C.c_float(gamma).value)):
+        raise L.AclganError("r1_gamma=%r: expected a finite number >= 0 (0 switches the R1 penalty off)" % (gamma,))
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise L.AclganError("r1_every=%r: expected an integer >= 1" % (every,))
+    if gamma > 0 and not math.isfinite(C.c_float(gamma * every).value):
+        raise L.AclganError("r1_gamma * r1_every = %r is no finite fp32 number" % (gamma * every,))
+    if gamma > 0 and hp.get("dis", {}).get("norm", "none") == "sn":
+        raise L.AclganError("r1_gamma > 0 with dis.norm: sn is not implemented (follow-up: fold the penalty through sigma and the "
+                            "power-iteration state); use dis.norm: none")
+    if gamma > 0 and augment_from_config(hp):
+        raise L.AclganError("r1_gamma > 0 with dis_augment is not implemented (follow-up: aclgan_diffaugment_fwd / _bwd around the R1 pass, "
+                            "the penalty through the affine augmentation); leave one of the two keys out")
+    return float(gamma), every
 
 
 AUG_SEED_OFFSET = 0x0A06            # the augmentation generator's seed = torch.initial_seed() + rank + this
@@ -314,6 +336,11 @@ class aclgan_Trainer:
         self.arch = arch_from_config(hp)
         self._ema_decay, self._ema_start, self.ema_display = ema_from_config(hp)
         self.augment = augment_from_config(hp)      # ACLGAN_AUG_* bits of dis_augment (0: off)
+        # R1 penalty on the real batches (r1_gamma > 0): the device float[2] of the penalties and the pass's scratch are made by the first pass
+        self.r1_gamma, self.r1_every = r1_from_config(hp)
+        self.r1_passes = 0
+        self._r1_pen = self._r1_scratch = None
+        self._r1_after = False
         # compute dtype of the heavy convolutions (not in the reference, which is fp32 only): "fp32" | "bf16" | "fp16"
         self.compute_dtype = str(compute_dtype or hp.get("compute_dtype", "fp32"))
         if self.compute_dtype not in L.DTYPE:
@@ -419,6 +446,8 @@ class aclgan_Trainer:
         self._losses = torch.zeros(len(L.LOSS_NAMES), device=self.device)
         for n in L.LOSS_NAMES:
             setattr(self, n, torch.zeros((), device=self.device))
+        # the penalties of the last R1 pass: 0 before the first (the zero a loss starts as: no tensor of their own while the key is off)
+        self.loss_dis_r1_A = self.loss_dis_r1_B = self.loss_dis_total
         self._zgen = None
         # fp16: dynamic loss scaling, state resident on the device (include/aclgan_hip.h: aclgan_bind_loss_scale)
         self._lscale = None
@@ -686,12 +715,21 @@ class aclgan_Trainer:
                 self._gscale[grp:grp + 1].copy_(self._lscale[0:1])
                 self._last_grp = grp
             fn = L.lib.aclgan_gen_update if which == "gen" else L.lib.aclgan_dis_update
+            # lazy R1: on the discriminator updates whose count BEFORE the update is a multiple of r1_every (the count is saved and resumed)
+            r1 = which == "dis" and self.r1_gamma > 0 and self._opt[grp]["steps"] % self.r1_every == 0
             if self.hip_graph and self._reducer is None and self._run_graph(which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev):
-                pass        # zero_grad + update replayed from the captured graph
+                # zero_grad + update replayed from the captured graph; the pass is not captured: eagerly after it, before Adam
+                if r1:
+                    self._r1_pass(x_a, x_b, B, H, W, st)
             else:
                 L.check(L.lib.aclgan_zero_grad(self._ctx, grp, st), "zero_grad")   # opt.zero_grad() (trainer.py:91,248)
                 if self._reducer is not None:
                     self._reducer.begin(grp)
+                # before the update: its bucket callbacks then fire after the last writer of every bucket.  (_r1_after, single process only: after
+                # it, the order a replayed update has -- tests measure what the order of the two accumulations is worth)
+                after = self._r1_after and self._reducer is None
+                if r1 and not after:
+                    self._r1_pass(x_a, x_b, B, H, W, st)
                 # an eager dis_update keeps its content encodings of x_a; the gen_update after it adopts them if nothing changed (_carry_state)
                 kept, self._carry, carry = self._carry, None, L.CARRY_OFF
                 if self.enc_reuse and not self.hip_graph:
@@ -701,6 +739,8 @@ class aclgan_Trainer:
                         carry = L.CARRY_ADOPT
                 L.check(L.lib.aclgan_ctx_carry_encodings(self._ctx, carry), "ctx_carry_encodings")
                 L.check(fn(self._ctx, L.ptr(x_a), L.ptr(x_b), L.ptr(zz), B, H, W, C.byref(hpc), L.ptr(self._losses), st), which + "_update")
+                if r1 and after:
+                    self._r1_pass(x_a, x_b, B, H, W, st)
             if getattr(self, "_sync_error", None) is not None:
                 raise self._sync_error
             self._allreduce_grads(grp)
@@ -716,6 +756,28 @@ class aclgan_Trainer:
             self._publish_losses(0, 12)
         else:
             self._publish_losses(12, 16)
+
+    def _r1_pass(self, x_a, x_b, B, H, W, st):
+        """aclgan_dis_r1 on (dis_A, x_a) and (dis_B, x_b) with gamma * r1_every, into the zeroed (or just written) DIS gradient buffer, on the
+        update's stream.  Under fp16 the library multiplies by the live loss scale, the one this update's gradients carry (grad_scale)."""
+        if self._r1_pen is None:
+            self._r1_pen = torch.zeros(2, device=self.device)
+        need = 0
+        for net in (self.dis_A, self.dis_B):
+            nb = L.lib.aclgan_dis_r1_scratch_bytes(self._ctx, net.net_id, B, H, W)
+            if not nb:
+                raise L.AclganError("dis_r1_scratch_bytes(%s, %d, %d, %d): %s" % (net.name, B, H, W, L.last_error()))
+            need = max(need, nb)
+        if self._r1_scratch is None or self._r1_scratch.numel() < need:
+            self._r1_scratch = None
+            self._r1_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        gamma = self.r1_gamma * self.r1_every
+        for i, (net, x) in enumerate(((self.dis_A, x_a), (self.dis_B, x_b))):
+            L.check(L.lib.aclgan_dis_r1(self._ctx, net.net_id, L.ptr(x), B, H, W, gamma, C.c_void_p(self._r1_pen.data_ptr() + 4 * i), None,
+                                        L.ptr(self._r1_scratch), st), "dis_r1(%s)" % net.name)
+        self.r1_passes += 1
+        vals = self._r1_pen.clone()      # fresh 0-d tensors per pass, like the losses of an update
+        self.loss_dis_r1_A, self.loss_dis_r1_B = vals[0], vals[1]
 
     # ---- HIP-graph replay of an update (opt-in, see __init__) ----
     def _run_graph(self, which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev=None):

@@ -558,6 +558,28 @@ int aclgan_diffaugment_fwd(int N, int H, int W, int C, int policy, const float* 
 int aclgan_diffaugment_bwd(int N, int H, int W, int C, int policy, const float* dy, const float* params, float* dx, int accumulate,
                            void* scratch, void* stream);
 
+/* R1 gradient penalty on real images (csrc/r1.hip; NOT in the reference; Mescheder et al. 2018).  For one
+ * discriminator D with outputs out_s (B,1,h_s,w_s), s < num_scales, on a real batch x (B,C,H,W) NCHW:
+ *   s_b = sum_s mean_pixels(out_s[b]),   G = d(sum_b s_b)/dx,   P = gamma/2 * (1/B) * sum_b ||G[b]||^2
+ * aclgan_dis_r1 writes P (without any loss scale) to *penalty_slot, G to grad_x if that is not NULL ((B,C,H,W) NCHW; for tests), and
+ * ACCUMULATES S dP/dW into that network's weight tensors of the bound ACLGAN_GROUP_DIS gradient buffer -- S the live fp16 loss scale
+ * ([0] of the state bound with aclgan_bind_loss_scale, read on the device) or 1: call it after aclgan_zero_grad, before or after
+ * aclgan_dis_update.  The bias gradients of the penalty are exactly zero (D without normalisation is piecewise linear in x): the bias
+ * slices are not touched.  net: ACLGAN_NET_DIS_A, ACLGAN_NET_DIS_B or ACLGAN_NET_DIS_2 (C = input_dim_a, input_dim_a, input_dim_b).
+ * The pass is no part of an update: aclgan_step_algorithmic_bytes / aclgan_step_executed_flops do not count it, nothing of it lives in
+ * the bound workspace (the carried encodings of aclgan_ctx_carry_encodings survive it), it runs on `stream` alone (no lane or pool
+ * stream) out of `scratch` (aclgan_dis_r1_scratch_bytes; launch-free, usable without a GPU, 0 where aclgan_dis_r1 would refuse the
+ * arguments; depends on the deterministic mode like every scratch size).
+ * Its convolutions are the fp32 operators (aclgan_conv2d_fwd_ws / _dgrad / _wgrad_ws) IN EVERY COMPUTE DTYPE: the penalty is a
+ * second-order term and the pass runs once every r1_every updates, so the 16-bit kernels are not used for it.  In deterministic mode
+ * two calls give the same bits (the sums of the new kernels have a fixed order in every mode).
+ * ACLGAN_EUNSUPPORTED under ACLGAN_NORM_SN; ACLGAN_EINVAL for another net, a null x / penalty_slot / scratch, unbound parameters, a
+ * negative or non-finite gamma, or a shape the discriminator cannot take (some layer would see fewer than 2 rows or columns) -- all
+ * before anything is enqueued.  After a failure in mid-flight the stream has been drained: the scratch may be freed. */
+size_t aclgan_dis_r1_scratch_bytes(aclgan_ctx* ctx, int net, int B, int H, int W);
+int aclgan_dis_r1(aclgan_ctx* ctx, int net, const float* x, int B, int H, int W, float gamma, float* penalty_slot, float* grad_x,
+                  void* scratch, void* stream);
+
 /* LinearBlock / MLP layer (networks.py:373-418, 280-292) and the style head's 1x1 conv on a pooled vector (networks.py:223):
  * y[b][o] = act(sum_i x[b][i] W[o][i] + bias[o]).  bwd: dy is modified in place by the activation backward; dx is
  * overwritten (may be NULL); dw, db accumulate (may be NULL). */
