@@ -145,6 +145,10 @@ SIGNATURES = {
     "aclgan_check_workspace": (ci, [vp, ci, ci, ci]),
     "aclgan_ctx_carry_encodings": (ci, [vp, ci]),
     "aclgan_ctx_set_augment": (ci, [vp, ci, vp, ci]),
+    "aclgan_lecam_state_floats": (sz, [vp]),
+    "aclgan_ctx_set_lecam": (ci, [vp, cf, cf, ci, vp]),
+    "aclgan_lsgan_lecam_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, ci, vp, vp, vp]),
+    "aclgan_lecam_fold": (ci, [vp, ci, cf, vp]),
     "aclgan_diffaugment_scratch_bytes": (sz, [ci, ci, ci, ci]),
     "aclgan_diffaugment_fwd": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "aclgan_diffaugment_bwd": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp]),

@@ -1,6 +1,7 @@
 // api.hip -- error plumbing and the operator-level C ABI of libaclgan_hip (see include/aclgan_hip.h).
 #include "common.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -384,6 +385,27 @@ int aclgan_lsgan_loss_multi(const float* const* o, const int* n, const float* ta
         t[i].target = target[i]; t[i].weight = weight[i]; t[i].gscale = gscale[i];
     }
     return lsgan_loss_batch(t.data(), nterms, (hipStream_t)stream);
+}
+int aclgan_lsgan_lecam_multi(const float* const* o, const int* n, const float* target, const float* weight, float* const* loss_slot,
+                             float* const* d_o, const float* gscale, const float* const* anchor, float* const* lecam_slot, float* const* stats,
+                             int nterms, float lambda, int start, const int* count, const float* lscale, void* stream) {
+    ACL_REQUIRE(o && n && target && weight && loss_slot && gscale && anchor && lecam_slot && stats && count && nterms >= 1 && nterms <= 1024,
+                "lsgan_lecam_multi: bad arguments");
+    ACL_REQUIRE(lambda >= 0.f && std::isfinite(lambda), "lsgan_lecam_multi: lambda = %g is no finite number >= 0", (double)lambda);
+    ACL_REQUIRE(start >= 0, "lsgan_lecam_multi: start = %d", start);
+    std::vector<LecamTerm> t((size_t)nterms);
+    for (int i = 0; i < nterms; ++i) {
+        ACL_REQUIRE(o[i] && n[i] > 0 && loss_slot[i] && anchor[i] && lecam_slot[i] && stats[i], "lsgan_lecam_multi: bad term %d", i);
+        t[i].ls.o = o[i]; t[i].ls.d_o = d_o ? d_o[i] : nullptr; t[i].ls.slot = loss_slot[i]; t[i].ls.n = n[i];
+        t[i].ls.target = target[i]; t[i].ls.weight = weight[i]; t[i].ls.gscale = gscale[i];
+        t[i].anchor = anchor[i]; t[i].lecam = lecam_slot[i]; t[i].stats = stats[i];
+    }
+    return lsgan_lecam_batch(t.data(), nterms, lambda, start, count, (hipStream_t)stream, lscale);
+}
+int aclgan_lecam_fold(float* state, int num_scales, float decay, void* stream) {
+    ACL_REQUIRE(state && num_scales >= 1, "lecam_fold: bad arguments");
+    ACL_REQUIRE(decay >= 0.f && decay < 1.f, "lecam_fold: decay = %g lies outside [0, 1)", (double)decay);
+    return lecam_fold(state, num_scales, decay, (hipStream_t)stream);
 }
 int aclgan_l1_loss(const float* a, int a_channels, const float* b, int64_t npix, float* loss_slot, float* d_a, float gscale, int d_accumulate,
                    void* stream) {

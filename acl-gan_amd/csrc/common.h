@@ -287,6 +287,15 @@ int lsgan_loss(const float* o, int n, float target, float weight, float* loss_sl
 struct LsganTerm { const float* o; float* d_o; float* slot; int n; float target, weight, gscale; };
 const int LSGAN_MAX_TERMS = 12;
 int lsgan_loss_batch(const LsganTerm* terms, int nterms, hipStream_t st, const float* lscale = nullptr);
+// ... with the LeCam term (include/aclgan_hip.h: aclgan_ctx_set_lecam): anchor = the anchor of the other class, lecam += weight*mean((o-anchor)^2)
+// unless count[0] == 0, stats[0] += weight*mean(o), stats[1] += weight; d_o gains lam_eff*(o-anchor), lam_eff = lambda from count[0] >= max(start, 1)
+// on, else 0 -- and then slot and d_o get the bits of lsgan_loss_batch.  count and the anchors are read before anything is written.
+struct LecamTerm { LsganTerm ls; const float* anchor; float* lecam; float* stats; };
+int lsgan_lecam_batch(const LecamTerm* terms, int nterms, float lambda, int start, const int* count, hipStream_t st, const float* lscale = nullptr);
+// state layout of aclgan_ctx_set_lecam (S = num_scales): anchors [3][S][2] | sums [3][S][2][2] | lecam slots [3] | count (int32)
+static inline size_t lecam_state_floats(int S) { return (size_t)18 * S + 4; }
+// anchors <- the update's weighted means (copy at count 0, else decay*a + (1-decay)*m; a non-finite m is skipped), sums <- 0, count += 1
+int lecam_fold(float* state, int num_scales, float decay, hipStream_t st);
 // L1 (trainer.py:61-62): loss_slot = mean|a[..,:3] - b|; a has a_stride channels (4: decoder output), b 3 channels.
 const int L1_PART_FLOATS = 1024;
 int l1_loss(const float* a, int a_stride, const float* b, int64_t npix, float* loss_slot, float* d_a, float gscale, int d_accumulate, hipStream_t st,

@@ -26,6 +26,7 @@
 #include <tuple>
 #include <mutex>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
@@ -242,6 +243,14 @@ struct aclgan_ctx {
     int aug_policy = 0;
     const float* aug_params = nullptr;
     int aug_rows = 0;
+    // ---- LeCam regularisation of the discriminators (aclgan_ctx_set_lecam; misc.hip: lsgan_lecam_batch / lecam_fold).
+    // lecam_state null: off -- dis_lsgan builds exactly the launches it built before the feature existed.  Otherwise the train passes that
+    // dis_update_impl builds (in_dis_update: set for the body of that function, real or dry, and nowhere else -- the fold that consumes the
+    // statistics follows only there) run the term kernel with the anchors of their discriminator, and the update ends with the fold.
+    float* lecam_state = nullptr;
+    float lecam_lambda = 0.f, lecam_decay = 0.f;
+    int lecam_start = 0;
+    bool in_dis_update = false;
     int carry_arm = ACLGAN_CARRY_OFF;            // what the caller armed for the next update
     int carry_call = ACLGAN_CARRY_OFF;           // mode of the update being built (dry runs: the mode being sized)
     int carry_mode = ACLGAN_CARRY_OFF;           // mode of the pass being built: carry_call inside the two carried passes, OFF elsewhere
@@ -1472,6 +1481,20 @@ static int dis_lsgan(aclgan_ctx& c, int net, bool train, Act* x, int nb, int row
         }
         if (o->need_grad) mark_written(o);
     }
+    if (train && c.in_dis_update && c.lecam_state) {      // (a train pass of dis_update: the only place a fold follows)
+        const int S = c.arch.dis_num_scales, D = net - ACLGAN_NET_DIS_A;
+        float* st = c.lecam_state;
+        std::vector<LecamTerm> lt(terms.size());
+        for (size_t j = 0; j < terms.size(); ++j) {
+            const int s = (int)(j / segs.size()), k = terms[j].target == 1.f ? 1 : 0;      // class = target: 1 the real side, 0 the fake side
+            lt[j].ls = terms[j];
+            lt[j].anchor = st + (D * S + s) * 2 + (1 - k);
+            lt[j].lecam = st + 18 * S + D;
+            lt[j].stats = st + 6 * S + ((D * S + s) * 2 + k) * 2;
+        }
+        RUN(lsgan_lecam_batch(lt.data(), (int)lt.size(), c.lecam_lambda, c.lecam_start, reinterpret_cast<const int*>(st + 18 * S + 3), c.st, c.lscale));
+        return ACLGAN_OK;
+    }
     RUN(lsgan_loss_batch(terms.data(), (int)terms.size(), c.st, c.lscale));
     return ACLGAN_OK;
 }
@@ -1807,6 +1830,11 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
 // ---- dis_update (trainer.py:254-292) ----
 static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, const float* z, int B, int H, int W,
                            const aclgan_hparams& hp, float* L) {
+    struct InDisUpdate {      // (cleared on every return path)
+        bool& f;
+        explicit InDisUpdate(bool& flag) : f(flag) { f = true; }
+        ~InDisUpdate() { f = false; }
+    } in_dis_update(c.in_dis_update);
     CHK(check_shape(c, B, H, W));
     const bool focus = hp.focus_loss > 0.f;      // trainer.py:266-276: same two branches as gen_update
     ACL_REQUIRE(c.arch.gen_output_dim == (focus ? 4 : 3), "focus_loss %s 0 needs gen.output_dim %d (trainer.py:266-276), the context was built with %d",
@@ -1816,6 +1844,10 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     if (!c.dry) {
         hipError_t e = hipMemsetAsync(L + ACLGAN_L_DIS_A, 0, sizeof(float) * 4, c.st);
         if (e != hipSuccess) return hip_fail(e, "memset losses");
+        if (c.lecam_state) {      // this update's three lecam slots start at zero, like its losses
+            e = hipMemsetAsync(c.lecam_state + 18 * c.arch.dis_num_scales, 0, sizeof(float) * 3, c.st);
+            if (e != hipSuccess) return hip_fail(e, "memset lecam slots");
+        }
     }
     CHK(c.lanes_begin(sw(SW_LANES)));
     CHK(pack_params(c));
@@ -1884,6 +1916,10 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     if (!c.dry) {
         hipLaunchKernelGGL(dis_total_kernel, dim3(1), dim3(1), 0, c.st, L, hp);
         ACL_CHECK_LAUNCH("dis_total_kernel");
+    }
+    if (c.lecam_state) {      // every launch that read anchors lies before the join: the anchors move for the NEXT update
+        c.count(2.0 * 4.0 * (double)lecam_state_floats(c.arch.dis_num_scales));
+        RUN(lecam_fold(c.lecam_state, c.arch.dis_num_scales, c.lecam_decay, c.st));
     }
     return run_tape(c);   // loss_dis_total.backward() (trainer.py:292)
 }
@@ -2169,6 +2205,17 @@ int aclgan_ctx_set_augment(aclgan_ctx* ctx, int policy, const float* params, int
     ctx->aug_policy = policy;
     ctx->aug_params = policy ? params : nullptr;
     ctx->aug_rows = policy ? rows : 0;
+    return ACLGAN_OK;
+}
+
+size_t aclgan_lecam_state_floats(aclgan_ctx* ctx) { return ctx ? lecam_state_floats(ctx->arch.dis_num_scales) : 0; }
+int aclgan_ctx_set_lecam(aclgan_ctx* ctx, float lambda, float decay, int start, float* state) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(lambda >= 0.f && std::isfinite(lambda), "set_lecam: lambda = %g is no finite number >= 0", (double)lambda);
+    ACL_REQUIRE(decay >= 0.f && decay < 1.f, "set_lecam: decay = %g lies outside [0, 1)", (double)decay);
+    ACL_REQUIRE(start >= 0, "set_lecam: start = %d is negative", start);
+    ctx->lecam_state = state;      // (NULL: off)
+    ctx->lecam_lambda = state ? lambda : 0.f; ctx->lecam_decay = state ? decay : 0.f; ctx->lecam_start = state ? start : 0;
     return ACLGAN_OK;
 }
 

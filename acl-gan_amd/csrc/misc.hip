@@ -790,6 +790,102 @@ int lsgan_loss_batch(const LsganTerm* terms, int nterms, hipStream_t st, const f
     return ACLGAN_OK;
 }
 
+// ---- LSGAN + LeCam (include/aclgan_hip.h: aclgan_ctx_set_lecam): the batch kernel with a second quadratic around the other class's anchor ----
+// three block sums behind one pair of barriers; component 0 is added in block_sum_t0's order (same wave tree, red[0] + red[1] + red[2] + red[3])
+__device__ __forceinline__ void block_sum3_t0(float& a, float& b, float& c) {
+    __shared__ float red[12];
+    a = wave_sum_m(a); b = wave_sum_m(b); c = wave_sum_m(c);
+    if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; red[w] = a; red[4 + w] = b; red[8 + w] = c; }
+    __syncthreads();
+    a = red[0] + red[1] + red[2] + red[3];
+    b = red[4] + red[5] + red[6] + red[7];
+    c = red[8] + red[9] + red[10] + red[11];
+    __syncthreads();
+}
+struct LecamBatch { LecamTerm t[LSGAN_MAX_TERMS]; int n; };
+__global__ void __launch_bounds__(256) lsgan_lecam_batch_kernel(LecamBatch b, const float* __restrict__ lscale, const int* __restrict__ count,
+                                                                float lambda, int start) {
+    // count and every anchor of the batch first, before the first write (one load per thread k < b.n, no dynamic index into the arguments)
+    __shared__ float s_anchor[LSGAN_MAX_TERMS];
+    const float* ap = nullptr;
+#pragma unroll
+    for (int k = 0; k < LSGAN_MAX_TERMS; ++k)
+        if ((int)threadIdx.x == k && k < b.n) ap = b.t[k].anchor;
+    if (ap) s_anchor[threadIdx.x] = ap[0];
+    const int cnt = count[0];
+    const float ls = lscale ? lscale[0] : 1.f;
+    __syncthreads();
+    const float lam = cnt >= (start > 1 ? start : 1) ? lambda : 0.f;
+    for (int k = 0; k < b.n; ++k) {
+        const LecamTerm lt = b.t[k];
+        const LsganTerm t = lt.ls;
+        const float a = s_anchor[k];
+        float s = 0.f, r = 0.f, m = 0.f;
+        float gscale = t.gscale;
+        if (lscale) gscale *= ls;
+        const float kk = gscale * t.weight * 2.f / (float)t.n;
+        if (lam == 0.f) {      // before the start: lsgan_batch_kernel's statements for slot and d_o, so its bits (no multiply by a zero factor)
+            for (int i = threadIdx.x; i < t.n; i += 256) {
+                const float o = t.o[i];
+                const float d = o - t.target, e = o - a;
+                s = fmaf(d, d, s);
+                r = fmaf(e, e, r);
+                m += o;
+                if (t.d_o) t.d_o[i] = kk * d;
+            }
+        } else {
+            for (int i = threadIdx.x; i < t.n; i += 256) {
+                const float o = t.o[i];
+                const float d = o - t.target, e = o - a;
+                s = fmaf(d, d, s);
+                r = fmaf(e, e, r);
+                m += o;
+                if (t.d_o) t.d_o[i] = kk * fmaf(lam, e, d);
+            }
+        }
+        block_sum3_t0(s, r, m);
+        if (threadIdx.x == 0) {      // one workgroup, terms in order, calls of one discriminator ordered on the stream: plain adds
+            t.slot[0] += t.weight * s / (float)t.n;
+            if (cnt > 0) lt.lecam[0] += t.weight * r / (float)t.n;
+            lt.stats[0] += t.weight * (m / (float)t.n);
+            lt.stats[1] += t.weight;
+        }
+        __syncthreads();
+    }
+}
+int lsgan_lecam_batch(const LecamTerm* terms, int nterms, float lambda, int start, const int* count, hipStream_t st, const float* lscale) {
+    for (int k0 = 0; k0 < nterms; k0 += LSGAN_MAX_TERMS) {
+        LecamBatch b;
+        b.n = std::min(LSGAN_MAX_TERMS, nterms - k0);
+        for (int k = 0; k < b.n; ++k) b.t[k] = terms[k0 + k];
+        for (int k = b.n; k < LSGAN_MAX_TERMS; ++k) b.t[k] = LecamTerm{};
+        hipLaunchKernelGGL(lsgan_lecam_batch_kernel, dim3(1), dim3(256), 0, st, b, lscale, count, lambda, start);
+        ACL_CHECK_LAUNCH("lsgan_lecam_batch_kernel");
+    }
+    return ACLGAN_OK;
+}
+// the fold: 6 S anchors, one thread each; every thread has read count before thread 0 advances it
+__global__ void __launch_bounds__(64) lecam_fold_kernel(float* __restrict__ state, int S, float decay) {
+    float* anchors = state;
+    float* sums = state + 6 * S;
+    int* count = reinterpret_cast<int*>(state + 18 * S + 3);
+    const int cnt = count[0];
+    __syncthreads();
+    for (int i = threadIdx.x; i < 6 * S; i += 64) {
+        const float sm = sums[2 * i], sw = sums[2 * i + 1];
+        const float m = sm / sw;      // (a class without a term: 0 / 0, skipped below)
+        if (sw > 0.f && isfinite(m)) anchors[i] = cnt == 0 ? m : decay * anchors[i] + (1.f - decay) * m;
+        sums[2 * i] = 0.f; sums[2 * i + 1] = 0.f;
+    }
+    if (threadIdx.x == 0) count[0] = cnt + 1;
+}
+int lecam_fold(float* state, int num_scales, float decay, hipStream_t st) {
+    ACL_REQUIRE(state && num_scales >= 1, "lecam_fold: bad arguments");
+    hipLaunchKernelGGL(lecam_fold_kernel, dim3(1), dim3(64), 0, st, state, num_scales, decay);
+    ACL_CHECK_LAUNCH("lecam_fold_kernel");
+    return ACLGAN_OK;
+}
+
 // ---- L1: loss_slot += mean|a[:, :3] - b|; d_a[pix][0..2] (+)= gscale*sign/N, channel 3 untouched (a_stride 4) ----
 __global__ void __launch_bounds__(256) l1_kernel(const float* __restrict__ a, int a_stride, const float* __restrict__ b, int64_t npix,
                                                  float* loss_slot, float* __restrict__ d_a, float gscale, int d_acc, const float* __restrict__ lscale,

@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 
 __all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "augment_from_config", "dis_norm_from_config", "draw_augment_params",
-           "ema_from_config", "hparams_from_config", "r1_from_config"]
+           "ema_from_config", "hparams_from_config", "lecam_from_config", "r1_from_config"]
 
 DIS_NORMS = ("none", "sn")    # dis.norm values the library implements (sn: SpectralNorm, networks.py:360-361,538-600)
 
@@ -103,6 +103,24 @@ def r1_from_config(hp):
         raise L.AclganError("r1_gamma > 0 with dis_augment is not implemented (follow-up: aclgan_diffaugment_fwd / _bwd around the R1 pass, "
                             "the penalty through the affine augmentation); leave one of the two keys out")
     return float(gamma), every
+
+
+def lecam_from_config(hp):
+    """The LeCam regulariser's keys (not in the reference; Tseng et al. 2021, eq. 7, two-sided, on the LSGAN outputs) as (lambda, decay, start):
+    lecam_lambda  float >= 0, default 0 = off: no buffer, no library call, the launches and bits of a run without the keys;
+    lecam_decay   float in [0, 1), default 0.99: the decay of the two anchors per discriminator and scale (mean D on real, mean D on fake);
+    lecam_start   int >= 0, default 1000: the anchors are tracked from the first discriminator update, the term acts from update start + 1 on
+                  (never on the first: it has no anchors yet).
+    The defaults are this project's choice; nobody has measured which values suit these datasets (README).  It composes with dis.norm sn,
+    dis_augment, r1_gamma and ema_decay: it only looks at discriminator outputs."""
+    lam, decay, start = hp.get("lecam_lambda", 0), hp.get("lecam_decay", 0.99), hp.get("lecam_start", 1000)
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not (0 <= lam and math.isfinite(C.c_float(lam).value)):
+        raise L.AclganError("lecam_lambda=%r: expected a finite number >= 0 (0 switches the LeCam regulariser off)" % (lam,))
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (0 <= decay and C.c_float(decay).value < 1):
+        raise L.AclganError("lecam_decay=%r: expected a number in [0, 1)" % (decay,))
+    if isinstance(start, bool) or not isinstance(start, int) or not 0 <= start < 2 ** 31:
+        raise L.AclganError("lecam_start=%r: expected an integer >= 0 (below 2**31)" % (start,))
+    return float(lam), float(decay), start
 
 
 AUG_SEED_OFFSET = 0x0A06            # the augmentation generator's seed = torch.initial_seed() + rank + this
@@ -369,6 +387,13 @@ class aclgan_Trainer:
         self._aug_dev = {}
         if self.augment:
             L.check(L.lib.aclgan_ctx_set_augment(self._ctx, self.augment, None, 0), "ctx_set_augment")
+        # LeCam regulariser (lecam_lambda > 0): anchors, per-update sums, the three published values and the update count in ONE persistent
+        # device tensor the context reads and writes stream-ordered (include/aclgan_hip.h: aclgan_ctx_set_lecam) -- a replayed graph too
+        self.lecam_lambda, self.lecam_decay, self.lecam_start = lecam_from_config(hp)
+        self._lecam = None
+        if self.lecam_lambda > 0:
+            self._lecam = torch.zeros(L.lib.aclgan_lecam_state_floats(self._ctx), dtype=torch.float32, device=self.device)
+            L.check(L.lib.aclgan_ctx_set_lecam(self._ctx, self.lecam_lambda, self.lecam_decay, self.lecam_start, L.ptr(self._lecam)), "ctx_set_lecam")
         # the lane scheduler's streams first, before anything else of this process creates one (the rank-0 broadcast below initialises the process
         # group's communicator and its stream): HIP binds streams to hardware queues in creation order (include/aclgan_hip.h, aclgan_warm_streams)
         if os.environ.get("ACLGAN_WARM_STREAMS", "1") not in ("", "0"):
@@ -448,6 +473,8 @@ class aclgan_Trainer:
             setattr(self, n, torch.zeros((), device=self.device))
         # the penalties of the last R1 pass: 0 before the first (the zero a loss starts as: no tensor of their own while the key is off)
         self.loss_dis_r1_A = self.loss_dis_r1_B = self.loss_dis_total
+        # ... and the LeCam values of the last dis_update, w * mean((D - anchor of the other side)^2) summed per discriminator, without lambda
+        self.loss_dis_lecam_A = self.loss_dis_lecam_B = self.loss_dis_lecam_2 = self.loss_dis_total
         self._zgen = None
         # fp16: dynamic loss scaling, state resident on the device (include/aclgan_hip.h: aclgan_bind_loss_scale)
         self._lscale = None
@@ -756,6 +783,10 @@ class aclgan_Trainer:
             self._publish_losses(0, 12)
         else:
             self._publish_losses(12, 16)
+            if self._lecam is not None:
+                s = 18 * self.arch.dis_num_scales
+                vals = self._lecam[s:s + 3].clone()
+                self.loss_dis_lecam_A, self.loss_dis_lecam_B, self.loss_dis_lecam_2 = vals[0], vals[1], vals[2]
 
     def _r1_pass(self, x_a, x_b, B, H, W, st):
         """aclgan_dis_r1 on (dis_A, x_a) and (dis_B, x_b) with gamma * r1_every, into the zeroed (or just written) DIS gradient buffer, on the
@@ -786,6 +817,8 @@ class aclgan_Trainer:
         key = (B, H, W, bytes(hpc), self._ws.data_ptr(), self._ws.numel(), self.compute_dtype, self.deterministic)
         if self.augment:      # (the captured kernels read the policy and the address of the rows; the rows themselves are refilled before every replay)
             key += (self.augment, aug_dev.data_ptr(), aug_dev.shape[0])
+        if self._lecam is not None:      # (lambda, decay and start are kernel arguments of the captured launches, the state's address too)
+            key += (self.lecam_lambda, self.lecam_decay, self.lecam_start, self._lecam.data_ptr())
         ent = self._graphs.get(which)
         if ent is None or ent["key"] != key:
             self._graphs[which] = {"key": key, "graph": None}
@@ -837,6 +870,10 @@ class aclgan_Trainer:
             broadcast_flat(self._ema)
         if self._tensors[L.GROUP_SN_STATE]:
             broadcast_flat(self._sn_state)   # spectral norm's u / v (not parameters, but every replica must start from the same)
+        if self._lecam is not None:
+            # LeCam anchors: every rank starts from rank 0's (here and after resume()), then keeps its own -- each rank sees its own shard,
+            # the anchors are not all-reduced; the parameter gradients are, as before
+            broadcast_flat(self._lecam)
         steps = torch.tensor([self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls], dtype=torch.int64, device=self.device)
         dist.broadcast(steps, 0)
         self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls = (int(v) for v in steps.tolist())
@@ -961,6 +998,29 @@ class aclgan_Trainer:
         self._require_ema("ema_reset()")
         self._ema.copy_(self._param[L.GROUP_GEN])
 
+    # ---- LeCam regulariser (lecam_lambda > 0; not in the reference) ----
+    @property
+    def lecam_updates(self):
+        """discriminator updates folded into the anchors so far (the device's count; one device->host copy); 0 while the key is off"""
+        if self._lecam is None:
+            return 0
+        return int(self._lecam[-1:].view(torch.int32).item())
+
+    def lecam_anchors(self):
+        """{'A', 'B', '2'}: per discriminator a (num_scales, 2) tensor (copies), [s][0] the moving average of its mean output on the fake side,
+        [s][1] on the real side (dis_2: pair_A1 / pair_A2).  The two drift apart when a discriminator memorises its real images."""
+        if self._lecam is None:
+            raise L.AclganError("lecam_anchors(): the LeCam regulariser is off (set lecam_lambda > 0)")
+        S = self.arch.dis_num_scales
+        a = self._lecam[:6 * S].clone().view(3, S, 2)
+        return {"A": a[0], "B": a[1], "2": a[2]}
+
+    def lecam_log_text(self):
+        """train.py's log-line suffix: the three values of the last dis_update and the first scale's anchors"""
+        a = self.lecam_anchors()
+        return (" lecam_A=%.4g lecam_B=%.4g lecam_2=%.4g" % (float(self.loss_dis_lecam_A), float(self.loss_dis_lecam_B), float(self.loss_dis_lecam_2)) +
+                "".join(" D_real_%s=%.4g D_fake_%s=%.4g" % (k, float(a[k][0, 1]), k, float(a[k][0, 0])) for k in ("A", "B", "2")))
+
     def sample(self, x_a, x_b, ema=False):
         """trainer.py:179-245: per-image eval forward; returns the reference's 9-tuple (focus branch) or 7-tuple (focus_loss == 0).
         ema=True: from the averaged generators (ema_weights())."""
@@ -1066,6 +1126,10 @@ class aclgan_Trainer:
             sd = self.ema_state_dict()
             torch.save({"AB": cpu(sd["AB"]), "BA": cpu(sd["BA"]), "updates": self.ema_updates, "decay": self._ema_decay},
                        os.path.join(snapshot_dir, "ema_%08d.pt" % (iterations + 1)))
+        if self._lecam is not None:
+            # the LeCam state as the device holds it (anchors, the count's four bytes).  The name holds neither "gen" nor "dis" either
+            # (decay: resume() warns when the resuming run's differs)
+            torch.save({"state": self._lecam.cpu().clone(), "decay": self.lecam_decay}, os.path.join(snapshot_dir, "lecam_%08d.pt" % (iterations + 1)))
 
     @staticmethod
     def _get_model_list(dirname, key):   # utils.py:211-220
@@ -1105,6 +1169,22 @@ class aclgan_Trainer:
                 import warnings
                 warnings.warn("aclgan_Trainer.resume: %s not found; the averaged generator starts from the resumed weights" % ema_name)
                 self.ema_reset()
+        if self._lecam is not None:
+            lecam_name = os.path.join(checkpoint_dir, "lecam_%08d.pt" % iterations)
+            if os.path.isfile(lecam_name):
+                sd = torch.load(lecam_name, map_location="cpu")
+                if tuple(sd["state"].shape) != tuple(self._lecam.shape):
+                    raise L.AclganError("resume: %s holds %d floats, dis.num_scales %d needs %d" % (lecam_name, sd["state"].numel(),
+                                                                                                   self.arch.dis_num_scales, self._lecam.numel()))
+                self._lecam.copy_(sd["state"].to(self.device, torch.float32))
+                if float(sd.get("decay", self.lecam_decay)) != self.lecam_decay:
+                    import warnings
+                    warnings.warn("aclgan_Trainer.resume: %s was written with lecam_decay %r, this run uses %r; the saved anchors continue under "
+                                  "the new decay" % (lecam_name, sd["decay"], self.lecam_decay))
+            else:
+                import warnings
+                warnings.warn("aclgan_Trainer.resume: %s not found; the LeCam anchors start again (the term acts after lecam_start more updates)" % lecam_name)
+                self._lecam.zero_()
         self._hp = hyperparameters
         self._setup_data_parallel()
         print("Resume from iteration %d" % iterations)

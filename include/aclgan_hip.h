@@ -276,6 +276,34 @@ int aclgan_ctx_carry_encodings(aclgan_ctx* ctx, int mode);
 #define ACLGAN_AUG_TRANSLATION 2
 #define ACLGAN_AUG_CUTOUT 4
 int aclgan_ctx_set_augment(aclgan_ctx* ctx, int policy, const float* params, int rows);
+/* LeCam regularisation of the discriminators (NOT in the reference; Tseng et al., CVPR 2021, "Regularizing Generative Adversarial Networks
+ * under Limited Data", eq. 7, in its two-sided quadratic form).  Per discriminator D (dis_A, dis_B, dis_2) and scale s
+ * the library keeps two anchors: moving averages of D's mean output on its real side (LSGAN target 1: x_a, x_b, pair_A2) and on its fake
+ * side (target 0).  With a state bound, every LSGAN term of aclgan_dis_update -- output map o of n elements, target t, reported weight w --
+ * becomes
+ *     loss slot (unchanged)  += w * mean((o - t)^2)
+ *     lecam slot of D        += w * mean((o - a[D][s][1-t])^2)                       (0 while count == 0)
+ *     d_o = S * gscale * w * (2/n) * [ (o - t) + lam_eff * (o - a[D][s][1-t]) ]
+ *     lam_eff = lambda if count >= max(start, 1) else 0                              (count is read on the device)
+ * S the live fp16 loss scale or 1; the anchors are constants of the gradient; aclgan_gen_update does not change.  After the lanes have
+ * joined one more launch folds the update's statistics:
+ *     m[D][s][k] = sum_{terms of class k} w * mean(o) / sum_{terms of class k} w
+ *     a[D][s][k] = m if count == 0, else decay * a + (1 - decay) * m;   a non-finite m leaves a as it is
+ *     count += 1;  the per-update sums are zeroed for the next update
+ * Every launch that reads anchors precedes the fold: an update sees the anchors the previous update left.  With lam_eff == 0 the loss
+ * slots and d_o hold exactly the bits of an update without a state.  The 16 losses keep their meaning and values.
+ * state: DEVICE memory of aclgan_lecam_state_floats(ctx) = 18 S + 4 floats (S = dis.num_scales), zero-initialised by the caller, D in the order
+ * dis_A, dis_B, dis_2, k = 0 fake side, 1 real side:
+ *     [0, 6 S)           anchors a[D][s][k] at (D * S + s) * 2 + k
+ *     [6 S, 18 S)        per-update sums at 6 S + ((D * S + s) * 2 + k) * 2: (sum of w * mean(o), sum of w)
+ *     [18 S, 18 S + 3)   the lecam slots of dis_A, dis_B, dis_2: this update's sum of w * mean((o - a)^2), without lambda (zeroed when an update starts)
+ *     [18 S + 3]         count, the number of updates folded so far, as an int32 in the float's four bytes
+ * aclgan_ctx_set_lecam keeps the pointer, not the contents (read and written stream-ordered, also under a captured graph); state == NULL
+ * switches the feature off (a context's default: the launches, buffers and bits of a context that never heard of it).  ACLGAN_EINVAL, with
+ * nothing enqueued, for a negative or non-finite lambda, a decay outside [0, 1) or start < 0.  aclgan_lecam_state_floats launches nothing
+ * and needs no GPU (0 for a null context); aclgan_step_algorithmic_bytes counts the fold while a state is bound. */
+size_t aclgan_lecam_state_floats(aclgan_ctx* ctx);
+int aclgan_ctx_set_lecam(aclgan_ctx* ctx, float lambda, float decay, int start, float* state);
 /* arena for ONE forward-only call below (encode / decode / discriminator forward) on (B,*,H,W) images: what
  * test.py:55-131 and trainer.sample need -- far smaller than a training step's, and without its shape constraints
  * (any H, W the networks accept, e.g. the 256x340 a Resize(256) of a non-square photo yields) */
@@ -616,6 +644,17 @@ int aclgan_lsgan_loss(const float* o, int n, float target, float weight, float* 
  * calls leaves there. */
 int aclgan_lsgan_loss_multi(const float* const* o, const int* n, const float* target, const float* weight, float* const* loss_slot,
                             float* const* d_o, const float* gscale, int nterms, void* stream);
+/* The same launch with the LeCam term of aclgan_ctx_set_lecam, on caller-supplied maps (what aclgan_dis_update runs while a state is
+ * bound): per term additionally anchor[i] (device float: the anchor of the OTHER class), lecam_slot[i] (+= weight * mean((o - anchor)^2)
+ * unless *count == 0) and stats[i] (device float[2]: += weight * mean(o), += weight).  count: device int32; lam_eff = lambda if
+ * *count >= max(start, 1), else 0 -- then loss_slot and d_o receive exactly the bits of aclgan_lsgan_loss_multi.  lscale (may be NULL):
+ * device float, the factor S of d_o.  One workgroup processes the terms in index order and reads count and its anchors before it
+ * writes anything; more than 12 terms run as several launches.  The slots and statistics may alias between terms, the maps may not. */
+int aclgan_lsgan_lecam_multi(const float* const* o, const int* n, const float* target, const float* weight, float* const* loss_slot,
+                             float* const* d_o, const float* gscale, const float* const* anchor, float* const* lecam_slot, float* const* stats,
+                             int nterms, float lambda, int start, const int* count, const float* lscale, void* stream);
+/* The fold of aclgan_ctx_set_lecam on a caller-supplied state of 18 num_scales + 4 floats (the layout above): one single-workgroup launch. */
+int aclgan_lecam_fold(float* state, int num_scales, float decay, void* stream);
 /* recon_criterion (trainer.py:61-62): *loss_slot += mean|a[..., :3] - b| over npix pixels; a has a_channels (3 or 4) NHWC
  * channels, b has 3; d_a (may be NULL) (+)= gscale*sign/(3*npix) on channels 0-2 */
 int aclgan_l1_loss(const float* a, int a_channels, const float* b, int64_t npix, float* loss_slot, float* d_a, float gscale,

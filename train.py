@@ -166,7 +166,9 @@ def main():
                   " ".join("%s=%.4g" % (n[5:], float(vals[i])) for i, n in enumerate(L.LOSS_NAMES)
                            if n in ("loss_gen_total", "loss_dis_total", "loss_idt_A", "loss_gen_adv_A")) +
                   # (r1_gamma > 0: the penalties of the last R1 pass; not among the 16 reference losses, not in losses.csv)
-                  (" r1_A=%.4g r1_B=%.4g" % (float(trainer.loss_dis_r1_A), float(trainer.loss_dis_r1_B)) if trainer.r1_gamma > 0 else ""))
+                  (" r1_A=%.4g r1_B=%.4g" % (float(trainer.loss_dis_r1_A), float(trainer.loss_dis_r1_B)) if trainer.r1_gamma > 0 else "") +
+                  # (lecam_lambda > 0: the regulariser's values of the last dis_update and the first scale's anchors, mean D on real / on fake)
+                  (trainer.lecam_log_text() if trainer.lecam_lambda > 0 else ""))
             loss_log.append(iterations + 1, vals.tolist())
         if display is not None and image_due(iterations, config, "image_save_iter"):      # train.py:83-90
             train_a, train_b, test_a, test_b = display
