@@ -306,7 +306,7 @@ int aclgan_norm_bwd_st(int kind, int act, int B, int HW, int C, const void* x, c
     return norm_bwd(kind, act, B, HW, C, x, y, dy, w, w_stride, mean, rstd, dx, dw, db, dres, dres_accumulate, scratch, (hipStream_t)stream, &s);
 }
 
-// the step's own variants of the two normalisation calls (engine.hip conv_block): statistics from a conv epilogue, storage codes, the fused
+// the step's own variants of the two normalisation calls (engine_graph.hip conv_block): statistics from a conv epilogue, storage codes, the fused
 // scale / shift kept from the forward for the backward's activation mask, and the LayerNorm gamma / beta totals deferred to a later launch
 int aclgan_norm_fwd_x(int kind, int act, int B, int HW, int C, const void* x, const float* w, const float* b, int w_stride, const void* residual,
                       void* y, float* mean, float* rstd, void* scratch, const float* stats, int stats_chunk, const int* storage, float* ss_out,

@@ -15,7 +15,7 @@ int hip_fail(hipError_t e, const char* what);
 
 // kernel launches issued by this library since load (measurement support: aclgan_launch_count; bench.py reports launches per step)
 extern std::atomic<long long> g_launches;
-// content-encoder passes a gen_update adopted from the dis_update before it instead of running them (engine.hip; tuning key enc_reuse_hits)
+// content-encoder passes a gen_update adopted from the dis_update before it instead of running them (engine_step.hip; tuning key enc_reuse_hits)
 extern std::atomic<long long> g_enc_reuse_hits;
 
 #define ACL_CHECK_LAUNCH(what)                                           \
@@ -231,7 +231,7 @@ int diffaugment_fwd(int N, int H, int W, int C, int policy, const float* x, cons
 int diffaugment_bwd(int N, int H, int W, int C, int policy, const float* dy, const float* params, float* dx, int accumulate, void* scratch, hipStream_t st);
 // R1 gradient penalty (r1.hip).  DisView: what the pass reads of a context -- one un-normalised discriminator's tensors inside the bound
 // DIS group (layer l < n_layer: the 4x4 stride-2 convolutions, l == n_layer: the 1x1 head; index s * (n_layer + 1) + l) and the bound
-// loss-scale state.  Filled by dis_view (engine.hip, where the context is defined): ACLGAN_EINVAL for a null context or a net that is no
+// loss-scale state.  Filled by dis_view (engine.hip; engine.h defines the context): ACLGAN_EINVAL for a null context or a net that is no
 // discriminator, ACLGAN_EUNSUPPORTED under spectral normalisation; w / dw are null while the group's buffers are not bound.
 struct DisView {
     int cin = 0, dim = 0, n_layer = 0, num_scales = 0;

@@ -310,7 +310,7 @@ def layer_norm_munit(x, gamma, beta):
 # "Upsample(2) + 5x5" layers rounds the MERGED 3x3 phase filters (forward / dgrad, interior pixels only).
 # --------------------------------------------------------------------------------------
 # Round 3 -- 16-bit STORAGE: under a 16-bit compute dtype the build also keeps the activations and activation gradients of its wide
-# layers in HBM in that dtype (acl-gan_amd/csrc/engine.hip::conv_block):
+# layers in HBM in that dtype (acl-gan_amd/csrc/engine_graph.hip::conv_block):
 #   * the output of every Conv2dBlock with Cout % 64 == 0 is stored rounded (after norm / activation / residual add) -- except the one
 #     that feeds the 7x7 image-side output layer and the last layer of every discriminator scale (their consumers are fp32 kernels);
 #   * the conv output in front of a normalisation layer is stored rounded when the layer runs on the 16-bit-storage kernels (no

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel time per roctx range (network pass) from a `rocprofv3 --kernel-trace --marker-trace` database of a run with ACLGAN_ROCTX=1
-(csrc/engine.hip: one range per forward pass of a network, "gen_BA.decode#2", and per block of backward closures, "bwd:gen_BA.decode#2").
+(csrc/engine.h PassScope, csrc/engine.hip run_tape: one range per forward pass of a network, "gen_BA.decode#2", and per block of backward closures, "bwd:gen_BA.decode#2").
 Kernels are attributed through their position in the launch order: ranges are host intervals, kernels are enqueued by the same host thread in
 program order, so the n-th launch issued inside a range is the n-th kernel (ordered by dispatch) after the launches before the range."""
 import sqlite3, sys

@@ -142,7 +142,7 @@ def test_bucket_callback_fires_after_the_last_writer(lanes):
 
 @pytest.mark.parametrize("lanes", [1, 3])
 def test_bucket_callback_fires_after_the_sn_fold(lanes):
-    """the same with dis.norm sn: the spectral-norm fold (csrc/engine.hip sn_begin_call) is the last writer of every weight_bar gradient --
+    """the same with dis.norm sn: the spectral-norm fold (csrc/engine_graph.hip sn_begin_call) is the last writer of every weight_bar gradient --
     a read-modify-write of the buffer after the call's weight-gradient kernels, pushed with the range of its layers' gradients"""
     _bucket_last_writer(lanes, "sn")
 

@@ -167,7 +167,7 @@ def launch_table(wl):
         if not ent["name"].startswith("dis_"):
             add(ent, B)                       # generator passes run at the step's batch, one call per use
             continue
-        # the discriminators run over JOINT batches (engine.hip dis_lsgan): gen_update dis_B (B), dis_A (x_A_fake | x_A2_fake: 2B),
+        # the discriminators run over JOINT batches (engine_graph.hip dis_lsgan): gen_update dis_B (B), dis_A (x_A_fake | x_A2_fake: 2B),
         # dis_2 (pair_A1 | pair_A2: 2B); dis_update dis_B (x_B_fake | x_b: 2B), dis_A (x_A_fake | x_A2_fake | x_a: 3B), dis_2 (2B).
         # The oracle calls every network once per input; dis_A / dis_B share their shapes, dis_2 differs in its first layer only.
         for m in ((2,) if ent["name"].startswith("dis_2") else (1, 2, 3)):
@@ -630,7 +630,7 @@ def check_16bit_layer(L, chk, g, ent, dt, seed, last_dec_res):
     s_bwd = f16 and d16 and w16 and L.lib.aclgan_conv16s_ok(C.byref(d_b), 1) == 1
     s_fwd = f16 and L.lib.aclgan_conv16s_ok(C.byref(d_f), 0) == 1 and Ci % 64 == 0
     fp32_passes = tuple(ps for ps, ok in (("fwd", f16), ("dgrad", d16), ("wgrad", w16)) if not ok)
-    # storage of this layer's tensors in the step (engine.hip conv_block): activations of 64-multiple widths are 16-bit unless they feed an
+    # storage of this layer's tensors in the step (engine_graph.hip conv_block): activations of 64-multiple widths are 16-bit unless they feed an
     # fp32-only consumer (out16); the conv output in front of a norm and the gradients are 16-bit where the 16-bit-storage kernels run
     out_st = code if (Co % 64 == 0 and ent["out16"]) else 0
     x_st = code if Ci % 64 == 0 else 0
