@@ -544,8 +544,10 @@ int aclgan_ctx_create_dis_norm(const aclgan_arch* arch, int dis_norm, aclgan_ctx
                 "spectral norm: at most %d normalised layers per discriminator", SN_MAX_LAYERS);
     aclgan_ctx* c = new aclgan_ctx();
     c->arch = *arch;
-    c->dis_norm = dis_norm;
-    const bool sn = dis_norm == ACLGAN_NORM_SN;
+    // dis.n_layer 1 leaves no layer to normalise: such a context is a norm-none context (joint discriminator batches instead of one pass per
+    // reference call, the same bits as dis.norm none)
+    const bool sn = dis_norm == ACLGAN_NORM_SN && arch->dis_n_layer > 1;
+    c->dis_norm = sn ? ACLGAN_NORM_SN : ACLGAN_NORM_NONE;
     build_gen(c->groups[0], "gen_AB", *arch);
     build_gen(c->groups[0], "gen_BA", *arch);
     build_dis(c->groups[1], "dis_A", arch->input_dim_a, *arch, sn ? &c->sn_layers[ACLGAN_NET_DIS_A] : nullptr, &c->sn);

@@ -6,8 +6,28 @@ namespace aclgan {
 
 std::atomic<long long> g_enc_reuse_hits{0};      // encoder passes adopted so far (tuning key enc_reuse_hits)
 
+// The smallest image side the architecture's own layers accept.  A 4x4 stride-2 layer reflect-pads by 1, so it needs a map of 2 at least and
+// halves it (floor); the pyramid halves with ceil (networks.py:33).  Scale s of a discriminator therefore needs ceil(H / 2^s) >= 2^n_layer.
+static int64_t dis_min_side(const aclgan_arch& a) {
+    if (a.dis_n_layer + a.dis_num_scales > 30) return INT32_MAX;
+    return (((int64_t)1 << a.dis_n_layer) - 1) * ((int64_t)1 << (a.dis_num_scales - 1)) + 1;
+}
+// content path: n_downsample such layers, then ResBlocks that reflect-pad the coarsest map by 1 (networks.py:230-245)
+static int64_t content_min_side(const aclgan_arch& a) { return a.gen_n_downsample > 29 ? INT32_MAX : (int64_t)2 << a.gen_n_downsample; }
+// style encoder: always four stride-2 layers (networks.py:126,212-228)
+static const int STYLE_MIN_SIDE = 16;
+
 static int check_shape(const aclgan_ctx& c, int B, int H, int W) {
     ACL_REQUIRE(B >= 1 && H >= 64 && W >= 64, "batch shape (%d,%d,%d): need B>=1 and H,W>=64 (third discriminator scale reflect-pads a >=2x2 map)", B, H, W);
+    // deeper architectures than the default need more than 64: refused here, by the key that asks for it, instead of by whichever
+    // convolution first meets a map it cannot reflect-pad
+    const aclgan_arch& a = c.arch;
+    const int64_t dmin = dis_min_side(a), cmin = content_min_side(a);
+    ACL_REQUIRE(H >= dmin && W >= dmin, "batch shape (%d,%d,%d): dis.n_layer %d at dis.num_scales %d needs H,W>=%lld (scale %d reflect-pads a >=2x2 map in each of its layers)",
+                B, H, W, a.dis_n_layer, a.dis_num_scales, (long long)dmin, a.dis_num_scales - 1);
+    ACL_REQUIRE(H >= cmin && W >= cmin, "batch shape (%d,%d,%d): gen.n_downsample %d needs H,W>=%lld (the ResBlocks reflect-pad a >=2x2 map)",
+                B, H, W, a.gen_n_downsample, (long long)cmin);
+    static_assert(STYLE_MIN_SIDE <= 64, "the style encoder's four stride-2 layers fit every admitted image");
     // the reference needs exactly this: the decoder upsamples x2^n_downsample from floor(H / 2^n) and the L1 identity
     // loss / focus blend compare it with the input (trainer.py:110-116,162-163)
     const int q = 1 << c.arch.gen_n_downsample;
@@ -369,7 +389,7 @@ int aclgan_forward_workspace_bytes(aclgan_ctx* ctx, int B, int H, int W, size_t*
             rc = input_act(c, nullptr, B, C, std::max(1, H / q), std::max(1, W / q), &x);
             if (!rc) rc = wrap_vec(c, nullptr, B, c.arch.gen_style_dim, 1.f, &s);
             if (!rc) rc = decode(c, ACLGAN_NET_GEN_AB, false, x, s, &o);
-        } else if (H >= 64 && W >= 64) {   // smaller images cannot pass through the third discriminator scale at all
+        } else if (std::min(H, W) >= std::max<int64_t>(64, dis_min_side(c.arch))) {   // smaller images cannot pass through the coarsest discriminator scale at all
             rc = input_act(c, nullptr, B, c.arch.input_dim_b, H, W, &x);
             if (!rc) rc = dis_forward(c, ACLGAN_NET_DIS_2, false, x, &outs);
         }

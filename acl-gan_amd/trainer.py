@@ -727,6 +727,9 @@ class aclgan_Trainer:
             aug = self._draw_augment(which, B, H, W)
         if z is None:
             z = self._draw_z(B)
+        if any(t.numel() != B * self.style_dim for t in z):      # (refused here, by name, before anything is copied or enqueued)
+            raise L.AclganError("z: expected (B, gen.style_dim %d, 1, 1) tensors for B = %d; got %s"
+                                % (self.style_dim, B, [tuple(t.shape) for t in z]))
         zz = torch.stack([t.reshape(B, self.style_dim).to(torch.float32) for t in z]).to(self.device).contiguous()
         hpc = hparams_from_config(hp)
         with torch.cuda.device(self.device):

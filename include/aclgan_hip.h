@@ -168,7 +168,8 @@ int aclgan_ctx_create(const aclgan_arch* arch, aclgan_ctx** out);
  * Under SN the discriminator group registers `cnns.S.L.conv.module.bias` then `...module.weight_bar` (OIHW, the reference's dis_opt order)
  * for L = 1 .. n_layer-1, and group ACLGAN_GROUP_SN_STATE holds `...module.weight_u` (Co) and `...module.weight_v` (Ci kh kw, in the
  * library's (kh, kw, ci) column order: the caller permutes it to the reference's (ci, kh, kw) at the state_dict boundary).  Every
- * discriminator forward (updates and aclgan_dis_forward) runs one power iteration per SN layer and overwrites u and v. */
+ * discriminator forward (updates and aclgan_dis_forward) runs one power iteration per SN layer and overwrites u and v.
+ * dis.n_layer 1 leaves no layer to normalise: ACLGAN_NORM_SN then creates the ACLGAN_NORM_NONE context (the same bits in deterministic mode). */
 int aclgan_ctx_create_dis_norm(const aclgan_arch* arch, int dis_norm, aclgan_ctx** out);
 void aclgan_ctx_destroy(aclgan_ctx* ctx);
 /* Call once, OUTSIDE any stream capture, on a context whose updates will be captured into a HIP graph (torch.cuda.graph around
@@ -233,7 +234,11 @@ int aclgan_bind_params16(aclgan_ctx* ctx, int group, void* w16, void* w16t);
  * buffer read by the caller (e.g. for an all-reduce) holds S*g.  NULL unbinds. */
 int aclgan_bind_loss_scale(aclgan_ctx* ctx, float* state);
 
-/* activation workspace for one update at the given batch shape (bytes); bind before stepping */
+/* activation workspace for one update at the given batch shape (bytes); bind before stepping.
+ * An update needs H and W to be multiples of 2^gen.n_downsample and at least max(64, (2^dis.n_layer - 1) 2^(dis.num_scales - 1) + 1,
+ * 2^(gen.n_downsample + 1)): every 4x4 stride-2 layer reflect-pads a map of 2 x 2 at least, and so do the ResBlocks.  A smaller image is
+ * refused here (and by every other dry run and by the updates themselves, before anything is enqueued) with the config key that asks for
+ * more and the minimum in aclgan_last_error(). */
 int aclgan_workspace_bytes(aclgan_ctx* ctx, int B, int H, int W, size_t* out);
 int aclgan_bind_workspace(aclgan_ctx* ctx, void* workspace, size_t bytes);
 /* ACLGAN_OK iff the bound workspace holds both updates at this batch shape with the tuning switches as they are now, else ACLGAN_ENOMEM

@@ -9,6 +9,9 @@ oracle (oracle/aclgan_oracle.py) and the HIP path are pinned against outputs of 
 reference implementation itself, captured here as *data only* (inputs, seeded weights identified by
 per-tensor checksums, expected outputs).  No reference source travels.
 
+arch_space.json (also alone: --arch-space-only) pins the nine architectures of tests/arch_space.py: losses and (sum, norm, max|.|) triples of
+one dis_update and one gen_update of the reference in float64; inputs and weights are regenerated from their seeds by the tests.
+
 Shims needed to import the reference on this CPU-only, torchvision-less box:
   * empty stub modules for torchvision (utils.py imports it at module level),
   * torch.Tensor.cuda -> identity (trainer.py hard-codes .cuda()),
@@ -317,7 +320,8 @@ def key_list():
     json.dump(order, open(os.path.join(HERE, "param_order.json"), "w"), indent=0)
 
 
-if __name__ == "__main__" and "--checkpoint-only" not in sys.argv and "--loop-only" not in sys.argv and "--plain-only" not in sys.argv:
+_ONLY = ("--checkpoint-only", "--loop-only", "--plain-only", "--arch-space-only")
+if __name__ == "__main__" and not any(f in sys.argv for f in _ONLY):
     torch.manual_seed(0)
     op_vectors()
     key_list()
@@ -483,3 +487,116 @@ if __name__ == "__main__" and "--loop-only" in sys.argv:
     loop_fixture()
 if __name__ == "__main__" and "--plain-only" in sys.argv:
     plain_fixture()
+
+
+def _r(v, digits=11):
+    """significant digits kept: 11 for losses, inputs and forward tensors (above fp64 summation-order noise); 8 for the seeded fp32 weights
+    (a checksum: the tests ask 1e-6); 6 for the gradients (the fp32 tests ask 3e-3; the fp64 oracle is pinned to them at full precision below)"""
+    return [float("%.*g" % (digits, x)) for x in v] if isinstance(v, list) else float("%.*g" % (digits, v))
+
+
+def arch_step_record(name):
+    """Compact record of one architecture of tests/arch_space.py: one dis_update and one gen_update of the REFERENCE in float64, each from
+    O.test_nets weights, as losses and (sum, norm, max|.|) triples of the inputs and forward tensors; per parameter, in parameters() order,
+    (sum, norm) of the weight and the norm of its gradient -- what keeps nine architectures in tens of KB.  Inputs and weights are regenerated from their seeds by the tests and
+    verified against the stored triples.  The number of discriminator scales and the width of z come from the config."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import arch_space as A
+    dd = torch.float64
+    cfg = A.arch_config(name, base_config())
+    cfg["_fill_seed"] = A.NET_SEED
+    B, H, W = A.arch_shape(name)
+    x_a, x_b, z = A.arch_inputs(name)
+    assert all(t.shape == (B, cfg["gen"]["style_dim"], 1, 1) for t in z)
+    xa, xb, zd = x_a.to(dd), x_b.to(dd), [t.to(dd) for t in z]
+    rec = {"config": cfg, "B": B, "H": H, "W": W, "net_seed": A.NET_SEED, "input_seed": A.INPUT_SEED,
+           "input_stats": {"x_a": _r(tstats(x_a)), "x_b": _r(tstats(x_b))}, "losses": {}, "grad_stats": {}, "param_stats_initial": {},
+           "fwd_stats": {}}
+    for i, t in enumerate(z):
+        rec["input_stats"]["z%d" % i] = _r(tstats(t))
+
+    def fresh():
+        tr = ref_trainer.aclgan_Trainer(cfg)
+        nets = fill_reference(tr, cfg)
+        return tr.double(), nets
+
+    tr, nets0 = fresh()
+    for net in O.OracleTrainer.NETS:
+        for k, p in getattr(tr, net).named_parameters():
+            rec["param_stats_initial"].setdefault(net, []).append(_r(tstats(p)[:2], 8))      # (in parameters() order: the names are the oracle's)
+    with torch.no_grad():
+        c1, _ = tr.gen_AB.encode(xa)
+        c2, s2 = tr.gen_BA.encode(xa)
+        xB4 = tr.gen_AB.decode(c1, zd[0])
+        xA4 = tr.gen_BA.decode(c2, cfg["alpha"] * zd[1])
+        xB = tr.focus_translation(xB4[:, :3], xa, xB4[:, 3:])
+        xA = tr.focus_translation(xA4[:, :3], xa, xA4[:, 3:])
+        c3, _ = tr.gen_BA.encode(xB)
+        xA24 = tr.gen_BA.decode(c3, zd[2])
+        xA2 = tr.focus_translation(xA24[:, :3], xB, xA24[:, 3:])
+        dA = tr.dis_A(xA)
+        d2 = tr.dis_2(torch.cat((xa, xA2), 1))
+        assert len(dA) == len(d2) == cfg["dis"]["num_scales"]
+        fw = {"c_1": c1, "c_2": c2, "s_2": s2, "dec_AB_c1_z1": xB4, "dec_BA_c2_z2": xA4, "x_B_fake": xB, "x_A_fake": xA, "c_3": c3,
+              "x_A2_fake": xA2}
+        for s in range(cfg["dis"]["num_scales"]):
+            fw["dis_A_xA_s%d" % s] = dA[s]
+            fw["dis_2_pA2_s%d" % s] = d2[s]
+        for k, v in fw.items():
+            rec["fwd_stats"][k] = {"shape": list(v.shape), "stats": _r(tstats(v))}
+    with RandnQueue(zd[:3]):
+        tr.dis_update(xa, xb, cfg)
+    ref_loss, ref_grads = {}, {}
+    for n in LOSS_NAMES_DIS:
+        ref_loss[n] = float(getattr(tr, n).detach())
+    for net in ("dis_A", "dis_B", "dis_2"):
+        for k, p in getattr(tr, net).named_parameters():
+            rec["grad_stats"].setdefault(net, []).append(_r(tstats(p.grad)[1], 6))
+            ref_grads[(net, k)] = p.grad.clone()
+    tr, _ = fresh()
+    with RandnQueue(zd[3:6]):
+        tr.gen_update(xa, xb, cfg)
+    for n in LOSS_NAMES_GEN:
+        ref_loss[n] = float(getattr(tr, n).detach())
+    for net in ("gen_AB", "gen_BA"):
+        for k, p in getattr(tr, net).named_parameters():
+            rec["grad_stats"].setdefault(net, []).append(_r(tstats(p.grad)[1], 6))
+            ref_grads[(net, k)] = p.grad.clone()
+    rec["losses"] = {n: _r(v) for n, v in ref_loss.items()}
+
+    # pin the oracle: in float64 it is the same function as the reference at this architecture too
+    n64 = {k: {n: t.to(dd) for n, t in v.items()} for k, v in nets0.items()}
+    od = O.OracleTrainer(cfg, nets=n64)
+    od.dis_update(xa, xb, zd[:3], apply=False)
+    losses = dict(od.losses)
+    g_orc = {(n, k): t.grad.clone() for n in ("dis_A", "dis_B", "dis_2") for k, t in od.nets[n].items()}
+    og = O.OracleTrainer(cfg, nets=n64)      # (shares the weight tensors with od: its update clears their gradients)
+    og.gen_update(xa, xb, zd[3:6], apply=False)
+    g_orc.update({(n, k): t.grad for n in ("gen_AB", "gen_BA") for k, t in og.nets[n].items()})
+    losses.update(og.losses)
+    worst = max(abs(losses[n] - v) / max(1e-6, abs(v)) for n, v in ref_loss.items())
+    gworst, zero = 0.0, []
+    for (net, k), g in ref_grads.items():
+        go = g_orc[(net, k)]
+        if float(g.abs().max()) == 0.0:
+            zero.append((net, k))
+        elif g.abs().max() > 1e-14:      # (a bias in front of an instance norm: mathematically zero, fp64 rounding noise in both)
+            gworst = max(gworst, ((go - g).abs().max() / g.abs().max()).item())
+    print("arch_space %-13s fp64 oracle vs fp64 reference: losses %.2e  grads %.2e  all-zero gradients %s" % (name, worst, gworst, zero))
+    assert worst < 1e-9 and gworst < 1e-8 and not zero, (name, worst, gworst, zero)
+    return rec
+
+
+def arch_space_fixture():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import arch_space as A
+    with open(os.path.join(HERE, "arch_space.json"), "w") as f:
+        f.write("{\n")
+        for i, name in enumerate(A.ARCHS):
+            f.write("%s: %s%s\n" % (json.dumps(name), json.dumps(arch_step_record(name), sort_keys=True, separators=(",", ":")),
+                                    "," if i + 1 < len(A.ARCHS) else ""))
+        f.write("}\n")
+
+
+if __name__ == "__main__" and ("--arch-space-only" in sys.argv or not any(f in sys.argv for f in _ONLY)):
+    arch_space_fixture()

@@ -112,12 +112,14 @@ def _hip_update_with_masks(tr, which, x_a, x_b, cfg, z, B, cap_bytes, used=None,
     return (chunks, signs, disagree) if bmap is not None else (chunks, signs)
 
 
-def _match(recorded, chunks, exclusive=False):
+def _match(recorded, chunks, exclusive=False, stride=13):
     """replay dictionary {oracle activation index: the HIP mask of the same block}; also the flip statistics.
     exclusive (spectral norm: every reference discriminator call is a pass of its own): each recorded chunk serves one oracle activation,
     and among the chunks that agree with it on >= 99 % the first one not yet taken wins -- the two real dis_A calls of dis_update see the
     same x_a with different sigmas, so their masks agree on nearly every element, and the engine runs one network's calls in the
-    reference's order.  used[j]: how many oracle activations took chunk j"""
+    reference's order.  used[j]: how many oracle activations took chunk j.
+    stride: the agreement is measured on every stride-th element; 1 where masks are small (a 1 x 1 x 64 mask of a coarse discriminator scale at
+    B = 1 leaves 5 samples at the default stride, and unrelated passes then agree on all of them by chance)"""
     by_shape = {}
     for j, ch in enumerate(chunks):
         by_shape.setdefault(tuple(ch.shape), []).append(j)
@@ -126,11 +128,11 @@ def _match(recorded, chunks, exclusive=False):
     for i, own in enumerate(recorded):
         cands = by_shape.get(tuple(own.shape), [])
         best, best_agree = None, 0.0
-        sub = own.flatten()[::13]
+        sub = own.flatten()[::stride]
         for j in cands:
             if exclusive and used[j]:
                 continue
-            a = (chunks[j].flatten()[::13] == sub).float().mean().item()
+            a = (chunks[j].flatten()[::stride] == sub).float().mean().item()
             if exclusive and a >= 0.99:
                 best, best_agree = j, a
                 break
