@@ -84,6 +84,10 @@ int conv_fwd_fast(const ConvGeom& g, const float* x, const float* w, const float
                   float* keepV = nullptr);
 size_t conv_fwd_fast_scratch_bytes(const ConvGeom& g);
 int conv_dgrad_fast(const ConvGeom& g, const float* dy, const float* w, float* dxp, float* dx, int accumulate, bool* direct, hipStream_t st);
+// conv_ring.hip (default plan, switch dgrad_ring): the border work of the input gradient added onto dx with atomics -- band = 0: the reflection
+// halo of a 3x3 / 4x4 stride-2 layer, band = 6: the band of a sub-pixel layer.  ACLGAN_EUNSUPPORTED: the caller keeps its own launch
+int conv_dgrad_ring(const ConvGeom& g, const float* dy, const float* w, float* dx, int band, hipStream_t st);
+double conv_dgrad_ring_flops(const ConvGeom& g, int band);      // the MFMA FLOPs of that launch (launch-free); < 0: not taken
 // also accumulates the bias gradient into db when db != nullptr
 int conv_wgrad_fast(const ConvGeom& g, const float* x, const float* dy, float* dw, float* db, hipStream_t st, void* scratch = nullptr, const float* haveV = nullptr);
 size_t conv_wgrad_fast_scratch_bytes(const ConvGeom& g);

@@ -477,6 +477,10 @@ int launch_dgrad_fast(const ConvGeom& g, DgFP p, hipStream_t st) {
 // stride-1 layers (what was measured), the caller's tile elsewhere.
 template <int WM, int WN, int TM, int TN>
 int launch_dgrad_halo(const ConvGeom& g, DgFP p, hipStream_t st) {
+    if (p.band == 0 && !p.ringpad && !p.dyv) {      // the ring kernel (conv_ring.hip) where it applies; dgrad_ring 0 keeps the launches below
+        const int rc = conv_dgrad_ring(g, p.dy, p.w, p.dxp, 0, st);
+        if (rc != ACLGAN_EUNSUPPORTED) return rc;
+    }
     if (p.band == 0 && !p.ringpad && g.k == 3 && g.s == 1 && g.Ci % 128 == 0 && WM == 2 && WN == 2 && TM == 2 && TN == 2)
         return launch_dgrad_fast<2, 2, 1, 2>(g, p, st);       // 64 x 128
     return launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
@@ -1010,6 +1014,8 @@ int up5_dgrad_t(const ConvGeom& g, const float* dy, const float* w, float* dx, i
         if (rc) return rc;
         return conv_fold(g, dxp, dx, 1, st);
     }
+    const int rcr = conv_dgrad_ring(g, dy, w, dx, p.band, st);      // the ring kernel (conv_ring.hip); dgrad_ring 0 keeps the launch below
+    if (rcr != ACLGAN_EUNSUPPORTED) return rcr;
     return launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
 }
 
@@ -1211,7 +1217,8 @@ double conv_exec_flops(const ConvGeom& g, int which, bool f16) {
         const double ring_fwd = 2.0 * g.B * ringpix * g.Co * g.K;
         // input gradient: band of width 6 of the padded hi-res grid, ~9 of the 25 taps useful per position (tap lists, conv_fast_common.h::dg_row)
         const double band = (double)g.Hp * g.Wp - (double)std::max(0, g.Hp - 12) * std::max(0, g.Wp - 12);
-        const double ring_dg = 2.0 * g.B * band * g.Ci * g.Co * 9.0;
+        const double ring_new = f16 ? -1.0 : conv_dgrad_ring_flops(g, 6);      // (conv_ring.hip: one tap list per line of the band, counted exactly)
+        const double ring_dg = ring_new >= 0.0 ? ring_new : 2.0 * g.B * band * g.Ci * g.Co * 9.0;
         if (!f16 && conv_up5_wino_ok(g)) {
             if (which == 0) return (wino_fused_ok(g.B, g.Hi - 2, g.Wi - 2, g.Ci, g.Co, g.act, 4, 1) ? fused_flops(g.B, g.Hi - 2, g.Wi - 2, g.Ci, g.Co, 4, 1)
                                                                                                      : pipe_flops(g.B, g.Hi - 2, g.Wi - 2, g.Ci, g.Co, 4)) + ring_fwd;
@@ -1223,7 +1230,8 @@ double conv_exec_flops(const ConvGeom& g, int which, bool f16) {
         return phases + (which == 1 ? ring_dg : ring_fwd);
     }
     if (!f16 && !sw(SW_NOFAST) && g.Ci % 16 == 0 && conv_wino_ok(g)) {
-        const double halo = 2.0 * g.B * ((double)g.Hp * g.Wp - (double)g.Hi * g.Wi) * g.Ci * g.Co * 3.0;      // ring of the padded grid, 3 of 9 taps per position
+        const double halo_new = conv_dgrad_ring_flops(g, 0);
+        const double halo = halo_new >= 0.0 ? halo_new : 2.0 * g.B * ((double)g.Hp * g.Wp - (double)g.Hi * g.Wi) * g.Ci * g.Co * 3.0;      // ring of the padded grid, 3 of 9 taps per position
         if (which == 0) return wino_fused_ok(g.B, g.Hi, g.Wi, g.Ci, g.Co, g.act) && !conv_fwd_keep_bytes(g) ? fused_flops(g.B, g.Hi, g.Wi, g.Ci, g.Co, 1, 1)
                                                                                                               : pipe_flops(g.B, g.Hi, g.Wi, g.Ci, g.Co, 1);
         if (which == 1) return (wino_fused_ok(g.B, g.Hi, g.Wi, g.Co, g.Ci, ACLGAN_ACT_NONE) ? fused_flops(g.B, g.Hi, g.Wi, g.Co, g.Ci, 1, 1) : pipe_flops(g.B, g.Hi, g.Wi, g.Co, g.Ci, 1)) + halo;
@@ -1234,7 +1242,8 @@ double conv_exec_flops(const ConvGeom& g, int which, bool f16) {
     const bool s2k4_dg_direct = !sw(SW_NODIRECT);
     if (!f16 && !sw(SW_NOFAST) && which < 2 && conv_s2k4_wino_ok(g, which) && (which == 0 || s2k4_dg_direct)) {
         if (which == 0) return fused_flops(g.B, g.Ho, g.Wo, g.Ci, g.Co, 1, 4);
-        const double halo = 2.0 * g.B * ((double)g.Hp * g.Wp - (double)g.Hi * g.Wi) * g.Ci * g.Co * 2.0;      // 2 of the 4 taps of a parity class per ring position
+        const double halo_new = conv_dgrad_ring_flops(g, 0);
+        const double halo = halo_new >= 0.0 ? halo_new : 2.0 * g.B * ((double)g.Hp * g.Wp - (double)g.Hi * g.Wi) * g.Ci * g.Co * 2.0;      // 2 of the 4 taps of a parity class per ring position
         return fused_flops(g.B, g.Ho, g.Wo, g.Co, g.Ci, 4, 1) + halo;
     }
     // the input gradient of the first discriminator layers (4x4 stride 2, Cin 3 / 6) runs on conv_s2k4_thin_dgrad_kernel: VALU only, no MFMA

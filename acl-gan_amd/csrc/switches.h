@@ -7,7 +7,7 @@ namespace aclgan {
 
 enum SwitchId {
     // update scheduler (engine.hip, engine_graph.hip, engine_step.hip); settable
-    SW_LANES, SW_U_BATCH, SW_NORM_MASK, SW_MLP_FUSED, SW_FAULT_AT, SW_ENC_REUSE,
+    SW_LANES, SW_U_BATCH, SW_NORM_MASK, SW_MLP_FUSED, SW_FAULT_AT, SW_ENC_REUSE, SW_DGRAD_RING,
     // kernel variants; settable
     SW_GLDS_TILE, SW_WINO_X3, SW_WINO_FUSED, SW_WINO_WGRAD_FUSED, SW_WINO_S2K4, SW_DGRAD16S_DIRECT, SW_FWD16_PATCH,
     // environment only

@@ -47,6 +47,7 @@ const Switch kSwitches[SW_COUNT] = {
     {"mlp_fused",         "ACLGAN_MLP_FUSED",         1,  R_BOOL,  0, 0,       SETTABLE | EMPTY_UNSET, nullptr},
     {"fault_at",          nullptr,                    -1, R_INT,   0, 0,       SETTABLE, nullptr},
     {"enc_reuse",         nullptr,                    1,  R_BOOL,  0, 0,       SETTABLE, nullptr},
+    {"dgrad_ring",        nullptr,                    1,  R_BOOL,  0, 0,       SETTABLE, nullptr},
     {"glds_tile",         "ACLGAN_GLDS_TILE",         0,  R_CLAMP, 0, INT_MAX, SETTABLE, nullptr},
     {"wino_x3",           "ACLGAN_WINO_X3",           0,  R_BOOL,  0, 0,       SETTABLE, nullptr},
     {"wino_fused",        "ACLGAN_WINO_FUSED",        1,  R_LOW4,  0, 2,       SETTABLE, nullptr},

@@ -466,6 +466,10 @@ int aclgan_conv2d_fwd16s(const aclgan_conv_desc* d, int dtype, const void* x16, 
  * key "wino_s2k4" (round 6): 1 (default) = the 4x4 stride-2 reflect-pad-1 layers (networks.py:41, 216-221, 236-241) run as four parity phases
  * of the same one-launch Winograd kernel wherever "wino_fused" sends them there (1: a cost model per shape, 2: every eligible shape) --
  * forward and the interior of the input gradient; 0 = they keep the direct implicit-GEMM kernels (ACLGAN_NOWINOS2=1).
+ * key "dgrad_ring": 1 (default) = on the default (atomics) plan the border work of the fp32 input gradient -- reflection halo of the 3x3 and 4x4
+ * stride-2 layers, band of the sub-pixel layers -- runs on conv_dgrad_ring_kernel (csrc/conv_ring.hip: host-made segments with one tap list each,
+ * eight k-tiles of loads in flight), 0 = on the halo launches of conv_dgrad_fast_kernel as before.  Same values up to the order of the atomics;
+ * the deterministic plan does not depend on it.  No environment variable.
  * key "fwd16_patch" (round 5): 1 (default) = the 3x3 stride-1 layers on 32- / 64-pixel-wide maps (the ResBlock convolutions) take
  * conv_fwd16p_kernel (csrc/conv_glds16.hip: the reflect-padded input patch of a 256-pixel tile stays in LDS for all nine taps; 2 = its
  * counter-phase schedule, a measured alternative), 0 = conv_fwd16s.
