@@ -181,6 +181,9 @@ SIGNATURES = {
     "aclgan_norm_scratch_bytes": (sz, [ci, ci, ci]),
     "aclgan_avgpool3s2_fwd": (ci, [ci, ci, ci, ci, vp, vp, vp]),
     "aclgan_avgpool3s2_bwd": (ci, [ci, ci, ci, ci, vp, vp, ci, vp]),
+    "aclgan_grad_clip_state_floats": (sz, []),
+    "aclgan_bind_grad_clip": (ci, [vp, ci, cf, vp]),
+    "aclgan_grad_clip_flat": (ci, [vp, i64, cf, vp, vp]),
     "aclgan_adam_flat": (ci, [vp, vp, vp, vp, i64, C.POINTER(Adam), ci, vp]),
     "aclgan_adam_flat_ema": (ci, [vp, vp, vp, vp, vp, i64, C.POINTER(Adam), ci, cf, ci, vp]),
     "aclgan_linear_fwd": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp]),

@@ -452,6 +452,9 @@ int aclgan_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, co
     ACL_REQUIRE(p && g && m && v && opt, "adam: null buffer");
     return adam_flat(p, g, m, v, n, opt, step, (hipStream_t)stream);
 }
+int aclgan_grad_clip_flat(const float* g, int64_t n, float max_norm, float* state, void* stream) {
+    return gradnorm_launch(g, n, max_norm, state, nullptr, (hipStream_t)stream);
+}
 int aclgan_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* opt, int step, float decay, int mode, void* stream) {
     ACL_REQUIRE(p && g && m && v && opt, "adam: null buffer");
     return adam_flat_ema(p, g, m, v, ema, n, opt, step, decay, mode, (hipStream_t)stream);

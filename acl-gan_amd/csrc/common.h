@@ -321,7 +321,13 @@ int adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, co
 // ... with the average: a skipped update (overflow) leaves ema untouched together with p, m and v
 int adam_flat_scaled_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
                          float* state, int group, hipStream_t st);
-
+// gradient norm and clip coefficient of a flat buffer into a clip state (gradnorm.hip; layout: include/aclgan_hip.h, aclgan_bind_grad_clip):
+// two launches.  lscale (optional): the bound loss-scale state -- the norm is taken of g / S and the pass raises lscale[3] for a non-finite g_i
+size_t grad_clip_state_floats();
+int gradnorm_launch(const float* g, int64_t n, float max_norm, float* clip, float* lscale, hipStream_t st);
+// Adam of a buffer with a clip state: gradnorm_launch, the clipped update (ema / state optional), the scale update under a loss scale
+int adam_flat_clipped(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
+                      float* state, int group, float max_norm, float* clip, hipStream_t st);
 
 // spectral normalisation (spectral.hip): one power iteration + normalised weight for up to SN_MAX_LAYERS Co x K matrices in four launches;
 // u (Co) is read and overwritten, v (K) overwritten; uf / vf (optional) receive copies of the new u / v, G (optional, Co x K) is zeroed;

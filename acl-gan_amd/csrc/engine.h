@@ -156,6 +156,9 @@ struct aclgan_ctx {
     unsigned short* w16[2] = {nullptr, nullptr};
     unsigned short* w16t[2] = {nullptr, nullptr};
     float* lscale = nullptr;
+    // gradient norm / clip state per group (aclgan_bind_grad_clip): null = off, the launches of a context without one
+    float* clip[2] = {nullptr, nullptr};
+    float clip_max[2] = {0.f, 0.f};
     // averaged generator (aclgan_bind_ema / aclgan_set_forward_weights): the average lives in a caller-owned buffer laid out like the generator
     // group's parameters.  read_ema is the selection of the call in flight: set by the forward-only entry points from fwd_weights, cleared by
     // reset_step -- updates and dry runs read the live weights whatever the switch says.  Everything that reads a weight goes through

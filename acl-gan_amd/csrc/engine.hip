@@ -714,6 +714,9 @@ int aclgan_adam_step(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int ste
     Group& g = ctx->groups[group];
     ACL_REQUIRE(g.param && g.grad && g.m && g.v, "param/grad/exp_avg/exp_avg_sq must all be bound");
     if (group == ACLGAN_GROUP_GEN) ctx->carry_drop();      // (the generators move: kept encodings are stale)
+    if (ctx->clip[group])
+        return adam_flat_clipped(g.param, g.grad, g.m, g.v, nullptr, g.numel, opt, step, 0.f, ACLGAN_EMA_COPY, ctx->lscale, group, ctx->clip_max[group],
+                                 ctx->clip[group], (hipStream_t)stream);
     if (ctx->lscale) return adam_flat_scaled(g.param, g.grad, g.m, g.v, g.numel, opt, step, ctx->lscale, group, (hipStream_t)stream);
     return adam_flat(g.param, g.grad, g.m, g.v, g.numel, opt, step, (hipStream_t)stream);
 }
@@ -732,8 +735,20 @@ int aclgan_adam_step_ema(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int
     Group& g = ctx->groups[group];
     ACL_REQUIRE(g.param && g.grad && g.m && g.v, "param/grad/exp_avg/exp_avg_sq must all be bound");
     ctx->carry_drop();
+    if (ctx->clip[group])
+        return adam_flat_clipped(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, ctx->lscale, group, ctx->clip_max[group],
+                                 ctx->clip[group], (hipStream_t)stream);
     if (ctx->lscale) return adam_flat_scaled_ema(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, ctx->lscale, group, (hipStream_t)stream);
     return adam_flat_ema(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, (hipStream_t)stream);
+}
+size_t aclgan_grad_clip_state_floats(void) { return grad_clip_state_floats(); }
+int aclgan_bind_grad_clip(aclgan_ctx* ctx, int group, float max_norm, float* state) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(group == ACLGAN_GROUP_GEN || group == ACLGAN_GROUP_DIS, "bind_grad_clip: group %d is neither ACLGAN_GROUP_GEN nor ACLGAN_GROUP_DIS", group);
+    ACL_REQUIRE(!state || max_norm > 0.f, "bind_grad_clip: max_norm = %g is neither a finite number > 0 nor +inf", (double)max_norm);      // (false for NaN)
+    ctx->clip[group] = state;      // (NULL: off)
+    ctx->clip_max[group] = state ? max_norm : 0.f;
+    return ACLGAN_OK;
 }
 int aclgan_set_forward_weights(aclgan_ctx* ctx, int which) {
     ACL_REQUIRE(ctx, "null ctx");

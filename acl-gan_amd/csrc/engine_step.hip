@@ -356,6 +356,9 @@ int aclgan_step_algorithmic_bytes(aclgan_ctx* ctx, int which, int B, int H, int 
     CHK(dry_update(c, which, B, H, W, which, c.last_mode[which], false, true));
     *out = c.alg_bytes + (4.0 + 28.0) * (double)c.groups[which].numel;    // + zero_grad + Adam (p, g, m, v read; p, m, v written)
     if (which == ACLGAN_GROUP_GEN && c.ema) *out += 8.0 * (double)c.groups[which].numel;      // + the average read and written by the same launch
+    // + the norm stage's read of the gradients (aclgan_bind_grad_clip).  Under a loss scale it replaces the overflow scan, which this count
+    // has never included: nothing is added there
+    if (c.clip[which] && !c.lscale) *out += 4.0 * (double)c.groups[which].numel;
     return ACLGAN_OK;
 }
 // the matrix-pipe FLOPs of the same update as the kernels EXECUTE them (conv_exec_flops: the cost of the path every layer's launchers choose

@@ -274,14 +274,17 @@ __global__ void grad_check_kernel(const float* __restrict__ g, int64_t n, float*
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) bad |= !isfinite(g[i]);
     if (bad) state[3] = 1.f;   // benign race: every writer stores the same value
 }
-template <bool EMA>
+// CLIP: a gradient-clip state is bound (aclgan_bind_grad_clip): clip[0] the norm, clip[1] the coefficient, clip[3] the updates skipped for a
+// non-finite norm -- written by gradnorm_finish_kernel (gradnorm.hip) just before this launch
+template <bool EMA, bool CLIP = false>
 __device__ __forceinline__ void adam_scaled_pass(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                  float b1, float b2, float eps, float wd, float lr, int step_host, const float* __restrict__ state, int group,
-                                                 float* __restrict__ ema, float d, int blend) {
+                                                 float* __restrict__ ema, float d, int blend, const float* __restrict__ clip = nullptr) {
     if (state[3] != 0.f) return;                   // overflow somewhere in this group's gradients: skip the update (p, m, v and the average stay)
-    const int step = step_host - (int)state[4 + group];   // skipped updates do not advance Adam's bias correction
+    if (CLIP && !isfinite(clip[0])) return;        // every gradient finite, their norm not: skipped as well (counted in clip[3])
+    const int step = step_host - (int)state[4 + group] - (CLIP ? (int)clip[3] : 0);   // skipped updates do not advance Adam's bias correction
     const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
-    const float step_size = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2)), inv = state[1];
+    const float step_size = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2)), inv = CLIP ? state[1] * clip[1] : state[1];
     adam_pass<true, EMA>(p, g, m, v, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, inv, ema, d, blend);
 }
 __global__ void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -292,6 +295,41 @@ __global__ void adam_scaled_ema_kernel(float* __restrict__ p, const float* __res
                                        int64_t n, float b1, float b2, float eps, float wd, float lr, int step_host, const float* __restrict__ state, int group,
                                        float* __restrict__ ema, float d, int blend) {
     adam_scaled_pass<true>(p, g, m, v, n, b1, b2, eps, wd, lr, step_host, state, group, ema, d, blend);
+}
+__global__ void adam_scaled_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                        int64_t n, float b1, float b2, float eps, float wd, float lr, int step_host, const float* __restrict__ state, int group,
+                                        const float* __restrict__ clip) {
+    adam_scaled_pass<false, true>(p, g, m, v, n, b1, b2, eps, wd, lr, step_host, state, group, nullptr, 0.f, 0, clip);
+}
+__global__ void adam_scaled_clip_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                            int64_t n, float b1, float b2, float eps, float wd, float lr, int step_host, const float* __restrict__ state, int group,
+                                            const float* __restrict__ clip, float* __restrict__ ema, float d, int blend) {
+    adam_scaled_pass<true, true>(p, g, m, v, n, b1, b2, eps, wd, lr, step_host, state, group, ema, d, blend, clip);
+}
+// Clipped Adam without a loss scale: g * coef in place of g.  step_size / inv_sqrt_bc2 are adam_launch's host values for step_host: used as
+// they are until the first skipped update (the bits of adam_kernel while coef == 1), recomputed here for step_host - clip[3] after one.
+template <bool EMA>
+__device__ __forceinline__ void adam_clip_pass(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                               float b1, float b2, float eps, float wd, float lr, int step_host, float step_size, float inv_sqrt_bc2,
+                                               const float* __restrict__ clip, float* __restrict__ ema, float d, int blend) {
+    if (!isfinite(clip[0])) return;                // non-finite norm: skip the update (p, m, v and the average stay; counted in clip[3])
+    const int skipped = (int)clip[3];
+    if (skipped != 0) {
+        const int step = max(step_host - skipped, 1);
+        const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
+        step_size = (float)((double)lr / bc1); inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
+    adam_pass<true, EMA>(p, g, m, v, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, clip[1], ema, d, blend);
+}
+__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 int64_t n, float b1, float b2, float eps, float wd, float lr, int step_host, float step_size, float inv_sqrt_bc2,
+                                 const float* __restrict__ clip) {
+    adam_clip_pass<false>(p, g, m, v, n, b1, b2, eps, wd, lr, step_host, step_size, inv_sqrt_bc2, clip, nullptr, 0.f, 0);
+}
+__global__ void adam_clip_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                     int64_t n, float b1, float b2, float eps, float wd, float lr, int step_host, float step_size, float inv_sqrt_bc2,
+                                     const float* __restrict__ clip, float* __restrict__ ema, float d, int blend) {
+    adam_clip_pass<true>(p, g, m, v, n, b1, b2, eps, wd, lr, step_host, step_size, inv_sqrt_bc2, clip, ema, d, blend);
 }
 __global__ void scale_update_kernel(float* state, int group) {
     state[7] = state[0];      // the scale the gradient buffers of THIS update carry (readable after the scale has moved on)
@@ -322,6 +360,43 @@ static int adam_scaled_launch(float* p, const float* g, float* m, float* v, floa
     }
     hipLaunchKernelGGL(scale_update_kernel, dim3(1), dim3(1), 0, st, state, group);
     ACL_CHECK_LAUNCH("scale_update_kernel");
+    return ACLGAN_OK;
+}
+// Adam of a group with a gradient-clip state: norm stage (gradnorm.hip; under a loss scale it also does the overflow scan), then the clipped
+// update, then -- under a loss scale -- the scale update.  ema == nullptr: without the average; state == nullptr: without a loss scale.
+int adam_flat_clipped(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
+                      float* state, int group, float max_norm, float* clip, hipStream_t st) {
+    ACL_REQUIRE(step >= 1 && clip && (group == 0 || group == 1), "adam (clipped): bad arguments");
+    if (ema) { const int rc = ema_args_ok(ema, decay, mode); if (rc) return rc; }
+    const int rc = gradnorm_launch(g, n, max_norm, clip, state, st);
+    if (rc) return rc;
+    const int grid = (int)std::min<int64_t>(cdiv64(n, 256), 16384);
+    const int blend = mode == ACLGAN_EMA_BLEND ? 1 : 0;
+    if (state) {
+        if (ema) {
+            hipLaunchKernelGGL(adam_scaled_clip_ema_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay, o->lr, step,
+                               (const float*)state, group, (const float*)clip, ema, decay, blend);
+            ACL_CHECK_LAUNCH("adam_scaled_clip_ema_kernel");
+        } else {
+            hipLaunchKernelGGL(adam_scaled_clip_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay, o->lr, step,
+                               (const float*)state, group, (const float*)clip);
+            ACL_CHECK_LAUNCH("adam_scaled_clip_kernel");
+        }
+        hipLaunchKernelGGL(scale_update_kernel, dim3(1), dim3(1), 0, st, state, group);
+        ACL_CHECK_LAUNCH("scale_update_kernel");
+        return ACLGAN_OK;
+    }
+    const double bc1 = 1.0 - pow((double)o->beta1, step), bc2 = 1.0 - pow((double)o->beta2, step);
+    const float step_size = (float)(o->lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));      // (adam_launch's expressions)
+    if (ema) {
+        hipLaunchKernelGGL(adam_clip_ema_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay, o->lr, step,
+                           step_size, inv_sqrt_bc2, (const float*)clip, ema, decay, blend);
+        ACL_CHECK_LAUNCH("adam_clip_ema_kernel");
+    } else {
+        hipLaunchKernelGGL(adam_clip_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, o->beta1, o->beta2, o->eps, o->weight_decay, o->lr, step,
+                           step_size, inv_sqrt_bc2, (const float*)clip);
+        ACL_CHECK_LAUNCH("adam_clip_kernel");
+    }
     return ACLGAN_OK;
 }
 int adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, float* state, int group, hipStream_t st) {

@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 
 __all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "augment_from_config", "dis_norm_from_config", "draw_augment_params",
-           "ema_from_config", "hparams_from_config", "lecam_from_config", "r1_from_config"]
+           "ema_from_config", "grad_clip_from_config", "hparams_from_config", "lecam_from_config", "r1_from_config"]
 
 DIS_NORMS = ("none", "sn")    # dis.norm values the library implements (sn: SpectralNorm, networks.py:360-361,538-600)
 
@@ -123,7 +123,29 @@ def lecam_from_config(hp):
     return float(lam), float(decay), start
 
 
-AUG_SEED_OFFSET = 0x0A06            # the augmentation generator's seed = torch.initial_seed() + rank + this
+def grad_clip_from_config(hp):
+    """The gradient-norm keys (not in the reference; torch.nn.utils.clip_grad_norm_ per optimizer group, on the device) as (gen, dis), the
+    max_norm of each group, 0 = off:
+    grad_clip      number > 0 or .inf, default 0 = off: no buffer, no library call, the launches and bits of a run without the keys.  Both groups.
+                   .inf is monitor and guard: the norms are read out, nothing is clipped, an update with a non-finite norm is skipped;
+    grad_clip_gen  optional override for the generators' group (0 switches that group off);
+    grad_clip_dis  likewise for the discriminators' group.
+    No bound is shipped: nobody has measured which suits these datasets (README: read the logged norms first).  It composes with dis.norm sn,
+    dis_augment, r1_gamma, lecam_lambda, ema_decay, hip_graph and data-parallel runs: it only looks at the finished gradient buffer."""
+    out = []
+    for key in ("grad_clip", "grad_clip_gen", "grad_clip_dis"):
+        if key not in hp:
+            out.append(None if key != "grad_clip" else 0.0)
+            continue
+        v = hp[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v >= 0) or (v > 0 and not C.c_float(v).value > 0):
+            raise L.AclganError("%s=%r: expected a number > 0 or .inf (0 switches the gradient norm, the clip and the guard off)" % (key, v))
+        out.append(float(v))
+    both, gen, dis = out
+    return (both if gen is None else gen, both if dis is None else dis)
+
+
+AUG_SEED_OFFSET = 0x0A06           # the augmentation generator's seed = torch.initial_seed() + rank + this
 
 
 def draw_augment_params(policy, rows, H, W, generator=None):
@@ -487,6 +509,15 @@ class aclgan_Trainer:
         # (grad_scale(grp)); the two groups are updated at different live scales whenever one of them overflowed in between
         self._gscale = None if self._lscale is None else torch.zeros(2, dtype=torch.float32, device=self.device)
         self._last_grp = None
+        # gradient norm / clip / guard (grad_clip*): per group one persistent device tensor the optimizer step reads and writes stream-ordered
+        # (include/aclgan_hip.h: aclgan_bind_grad_clip).  Off: no tensor, no call; the two readouts stay the zero a loss starts as
+        self.grad_clip = grad_clip_from_config(hp)
+        self._clip = [None, None]
+        self.grad_norm_gen = self.grad_norm_dis = self.loss_dis_total
+        for grp in (L.GROUP_GEN, L.GROUP_DIS):
+            if self.grad_clip[grp] > 0:
+                self._clip[grp] = torch.zeros(L.lib.aclgan_grad_clip_state_floats(), dtype=torch.float32, device=self.device)
+                L.check(L.lib.aclgan_bind_grad_clip(self._ctx, grp, self.grad_clip[grp], L.ptr(self._clip[grp])), "bind_grad_clip")
         self._ema = None
         self._fwd_ema = False
         # content encodings of x_a carried from a dis_update into the gen_update that follows it (_carry_state): the x_a tensor of the last
@@ -650,6 +681,24 @@ class aclgan_Trainer:
         v = self._lscale.cpu().tolist()
         return {"scale": v[0], "clean_updates": int(v[2]), "skipped_gen": int(v[4]), "skipped_dis": int(v[5])}
 
+    def grad_clip_state(self):
+        """{'gen': {...}, 'dis': {...}} with 'norm' and 'coef' of the group's last update (true-gradient units; coef 0: it was skipped) and the
+        counts 'clipped' / 'skipped' (skipped: for a non-finite norm; fp16 overflows are counted by loss_scale_state()).  None for a group
+        whose key is off.  One device->host copy, only when asked."""
+        on = [t[:4] for t in self._clip if t is not None]
+        vals = torch.stack(on).cpu().tolist() if on else []
+        out = {}
+        for name, t in zip(("gen", "dis"), self._clip):
+            v = vals.pop(0) if t is not None else None
+            out[name] = None if v is None else {"norm": v[0], "coef": v[1], "clipped": int(v[2]), "skipped": int(v[3])}
+        return out
+
+    def grad_clip_log_text(self):
+        """train.py's log-line suffix: both groups' last norms and the updates skipped so far (a group whose key is off shows nan / 0)"""
+        s = self.grad_clip_state()
+        norm = lambda k: s[k]["norm"] if s[k] else float("nan")      # noqa: E731
+        return " gnorm_G=%.4g gnorm_D=%.4g skipped=%d" % (norm("gen"), norm("dis"), sum(v["skipped"] for v in s.values() if v))
+
     def grad_scale(self, grp=None):
         """the factor a group's gradient buffers carry.  fp32 / bf16: 1.  fp16: the loss scale that group's last update ran with --
         the generator's and the discriminators' buffers differ whenever an overflow halved (or a clean run doubled) the live scale
@@ -782,6 +831,8 @@ class aclgan_Trainer:
                 L.check(L.lib.aclgan_adam_step_ema(self._ctx, grp, C.byref(adam), o["steps"], self._ema_decay, mode, st), "adam_step_ema")
             else:
                 L.check(L.lib.aclgan_adam_step(self._ctx, grp, C.byref(adam), o["steps"], st), "adam_step")   # opt.step()
+        if self._clip[grp] is not None:      # a fresh 0-d tensor per update, like the losses
+            setattr(self, "grad_norm_gen" if which == "gen" else "grad_norm_dis", self._clip[grp][0].clone())
         if which == "gen":
             self._publish_losses(0, 12)
         else:
@@ -1122,6 +1173,10 @@ class aclgan_Trainer:
             # live scale, clean-update counter and the SKIPPED-update counts Adam's bias-correction step excludes.  Adam's per-tensor
             # 'step' above counts applied + skipped updates (the reference's own counter semantics: one per optimizer.step() call).
             opt["aclgan_loss_scale_state"] = self._lscale.cpu().clone()
+        if any(t is not None for t in self._clip):
+            # another extra key: the eight leading floats of both groups' clip states (row 0 gen, row 1 dis; zeros for a group that is off).
+            # [3], the updates skipped for a non-finite norm, is part of Adam's bias-correction step like the loss scale's skip counts
+            opt["aclgan_grad_clip_state"] = torch.stack([torch.zeros(8) if t is None else t[:8].cpu() for t in self._clip])
         torch.save(opt, opt_name)
         if self._ema is not None:
             # the averaged generators, loadable wherever a gen_*.pt is (test.py --checkpoint).  The name holds neither "gen" nor "dis":
@@ -1154,6 +1209,18 @@ class aclgan_Trainer:
         self._load_opt_state_dict(L.GROUP_DIS, sd["dis"]); self._load_opt_state_dict(L.GROUP_GEN, sd["gen"])
         if self._lscale is not None and "aclgan_loss_scale_state" in sd:      # fp16: resume the loss scale and the skipped-update counts
             self._lscale.copy_(sd["aclgan_loss_scale_state"].to(self.device, torch.float32))
+        if any(t is not None for t in self._clip):
+            if "aclgan_grad_clip_state" in sd:
+                for t, row in zip(self._clip, sd["aclgan_grad_clip_state"]):
+                    if t is not None:
+                        t[:8].copy_(row.to(self.device, torch.float32))
+            else:
+                import warnings
+                warnings.warn("aclgan_Trainer.resume: optimizer.pt holds no aclgan_grad_clip_state (written with grad_clip off); the clipped and "
+                              "skipped counts start at 0")
+                for t in self._clip:
+                    if t is not None:
+                        t.zero_()
         # get_scheduler(..., iterations) (trainer.py:318-320, utils.py:263-271) builds StepLR(last_epoch=iterations).  The reference
         # pins torch 1.2.0 (acl-gan.yaml), whose _LRScheduler.__init__ ends with self.step(last_epoch): the scheduler resumes AT
         # last_epoch = iterations and (closed-form get_lr of that version) lr = lr0 * gamma ** (iterations // step_size).  torch >= 1.4

@@ -385,6 +385,39 @@ int aclgan_adam_step(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int ste
 int aclgan_bind_ema(aclgan_ctx* ctx, int group, float* ema);
 int aclgan_adam_step_ema(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int step, float decay, int mode, void* stream);
 int aclgan_set_forward_weights(aclgan_ctx* ctx, int which);
+/* ---- gradient norm per group: readout, clipping by global norm, non-finite updates skipped (NOT in the reference) ----
+ * With a state bound to a group, aclgan_adam_step / aclgan_adam_step_ema of that group do, on the caller's stream and without a host
+ * round trip:
+ *   1. one pass over the group's gradient buffer: n2 = sum_i (g_i * inv)^2, inv = 1/S of the bound loss-scale state or exactly 1 without
+ *      one; norm = sqrtf(n2), in true-gradient units.  Under a bound loss scale the same pass raises that state's overflow flag [3] for a
+ *      non-finite g_i: it takes the place of the scan, the buffer is still read once before Adam;
+ *   2. overflow flag set: the loss-scale machine runs as without a clip state (skip, halve, count); state[0] = norm, state[1] = 0, the
+ *      counters [2], [3] stay;
+ *   3. flag clear (or no loss scale) and norm not finite -- a clip-skip: param, exp_avg, exp_avg_sq and the average are not written;
+ *      state[0] = norm, state[1] = 0, state[3] += 1;
+ *   4. norm finite: coef = min(1, max_norm / (norm + 1e-6)) in fp32 (torch.nn.utils.clip_grad_norm_); state[0] = norm, state[1] = coef,
+ *      state[2] += 1 if coef < 1; Adam runs with g_i * (inv * coef) in place of g_i * inv, the weight decay added after the clip as
+ *      torch.optim.Adam adds it to a clipped .grad.
+ * Adam's bias-correction step is `step` - (loss-scale skips of the group) - state[3]: skipped updates never advance it.  While coef == 1
+ * and nothing has been skipped, param, exp_avg, exp_avg_sq and the average hold the bits of the same call without a state (without a loss
+ * scale the host-computed bias-correction factors are used until the first skip).  max_norm: a finite number > 0, or +inf = monitor and
+ * guard: coef is exactly 1, nothing is clipped, non-finite updates are still skipped.
+ * state: DEVICE memory of aclgan_grad_clip_state_floats() floats per group, caller-owned, zero-initialised:
+ *   [0] last norm  [1] last coefficient (0: that update was skipped)  [2] updates clipped  [3] updates skipped for a non-finite norm
+ *   [4..7] reserved, zero  [8..) the norm kernel's per-workgroup partial sums
+ * The counts are floats, like the loss-scale state's.  The sum has a fixed order (no atomics): the norm depends on the buffer, its length
+ * and its address modulo 16 bytes, not on the run.  Launches: gradnorm_part_kernel, gradnorm_finish_kernel, Adam (fp32 / bf16: two more
+ * than without a state); under a loss scale part, finish, Adam, the scale update (one more: the part kernel replaces the scan).
+ * aclgan_bind_grad_clip keeps the pointer, not the contents; state == NULL unbinds (max_norm is then not looked at): the launches and bits of a
+ * context that never heard of it.  ACLGAN_EINVAL, with nothing enqueued, for a group other than ACLGAN_GROUP_GEN / ACLGAN_GROUP_DIS or a max_norm that is NaN, <= 0 or
+ * -inf.  aclgan_grad_clip_state_floats launches nothing and needs no GPU.  aclgan_step_algorithmic_bytes counts the extra read of the
+ * gradients (4 B / parameter) for a group with a bound state on the fp32 / bf16 path; under a loss scale the pass replaces the scan, which
+ * that count has never included, so nothing is added there.
+ * aclgan_grad_clip_flat: steps 1, 3, 4 alone on any flat buffer (no context, no loss scale; g need not be 16-byte aligned): state[0..3]
+ * written as a group's call writes them. */
+size_t aclgan_grad_clip_state_floats(void);
+int aclgan_bind_grad_clip(aclgan_ctx* ctx, int group, float max_norm, float* state);
+int aclgan_grad_clip_flat(const float* g, int64_t n, float max_norm, float* state, void* stream);
 
 /* ---- forward-only entry points (test.py:55-70 / trainer.sample: encode / decode / D forward) ---- */
 /* AdaINGen.encode (networks.py:141-145): content (B,C,H/4,W/4) NCHW, style (B,style_dim) */

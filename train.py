@@ -168,7 +168,9 @@ def main():
                   # (r1_gamma > 0: the penalties of the last R1 pass; not among the 16 reference losses, not in losses.csv)
                   (" r1_A=%.4g r1_B=%.4g" % (float(trainer.loss_dis_r1_A), float(trainer.loss_dis_r1_B)) if trainer.r1_gamma > 0 else "") +
                   # (lecam_lambda > 0: the regulariser's values of the last dis_update and the first scale's anchors, mean D on real / on fake)
-                  (trainer.lecam_log_text() if trainer.lecam_lambda > 0 else ""))
+                  (trainer.lecam_log_text() if trainer.lecam_lambda > 0 else "") +
+                  # (grad_clip* on: the gradient norms of the last generator / discriminator update and the updates skipped for a non-finite norm)
+                  (trainer.grad_clip_log_text() if max(trainer.grad_clip) > 0 else ""))
             loss_log.append(iterations + 1, vals.tolist())
         if display is not None and image_due(iterations, config, "image_save_iter"):      # train.py:83-90
             train_a, train_b, test_a, test_b = display
