@@ -147,6 +147,9 @@ SIGNATURES = {
     "aclgan_ctx_set_augment": (ci, [vp, ci, vp, ci]),
     "aclgan_lecam_state_floats": (sz, [vp]),
     "aclgan_ctx_set_lecam": (ci, [vp, cf, cf, ci, vp]),
+    "aclgan_modeseek_scratch_bytes": (sz, [ci, i64]),
+    "aclgan_modeseek": (ci, [vp, vp, ci, i64, vp, vp, ci, cf, cf, vp, vp, vp, vp, ci, vp, vp]),
+    "aclgan_ctx_set_modeseek": (ci, [vp, cf, vp, ci, vp]),
     "aclgan_lsgan_lecam_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, ci, vp, vp, vp]),
     "aclgan_lecam_fold": (ci, [vp, ci, cf, vp]),
     "aclgan_diffaugment_scratch_bytes": (sz, [ci, ci, ci, ci]),

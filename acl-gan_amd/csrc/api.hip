@@ -455,6 +455,24 @@ int aclgan_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, co
 int aclgan_grad_clip_flat(const float* g, int64_t n, float max_norm, float* state, void* stream) {
     return gradnorm_launch(g, n, max_norm, state, nullptr, (hipStream_t)stream);
 }
+size_t aclgan_modeseek_scratch_bytes(int B, int64_t n_per_image) {
+    return B >= 1 && n_per_image >= 1 ? sizeof(float) * modeseek_scratch_floats(B, n_per_image) : 0;
+}
+int aclgan_modeseek(const float* a, const float* b, int B, int64_t n_per_image, const float* u, const float* u2, int style_dim, float u_scale,
+                    float weight, const float* loss_scale, float* out4, float* da, float* db, int accumulate, void* scratch, void* stream) {
+    // (everything modeseek_grad refuses is refused here, before the first launch)
+    ACL_REQUIRE(a && b && u && u2 && out4 && scratch, "modeseek: null image, noise, output or scratch");
+    ACL_REQUIRE(B >= 1 && B <= 65535 && n_per_image >= 1 && style_dim >= 1, "modeseek: B = %d (1 .. 65535), n_per_image = %lld (>= 1), style_dim = %d (>= 1)", B,
+                (long long)n_per_image, style_dim);
+    ACL_REQUIRE(std::isfinite(weight) && weight >= 0.f && std::isfinite(u_scale), "modeseek: weight = %g is no finite number >= 0, or u_scale = %g is not finite",
+                (double)weight, (double)u_scale);
+    ACL_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)u | (uintptr_t)u2 | (uintptr_t)out4 | (uintptr_t)da | (uintptr_t)db | (uintptr_t)loss_scale | (uintptr_t)scratch) & 3) == 0,
+                "modeseek: a float buffer is not 4-byte aligned");
+    int rc = modeseek_part(a, b, 0, B, n_per_image, (float*)scratch, (hipStream_t)stream);
+    if (!rc) rc = modeseek_grad(a, b, 0, B, n_per_image, (const float*)scratch, u, u2, style_dim, u_scale, weight, loss_scale, out4, da, db, accumulate ? 3 : 0,
+                                (hipStream_t)stream);
+    return rc;
+}
 int aclgan_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* opt, int step, float decay, int mode, void* stream) {
     ACL_REQUIRE(p && g && m && v && opt, "adam: null buffer");
     return adam_flat_ema(p, g, m, v, ema, n, opt, step, decay, mode, (hipStream_t)stream);

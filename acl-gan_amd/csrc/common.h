@@ -325,6 +325,14 @@ int adam_flat_scaled_ema(float* p, const float* g, float* m, float* v, float* em
 // two launches.  lscale (optional): the bound loss-scale state -- the norm is taken of g / S and the pass raises lscale[3] for a non-finite g_i
 size_t grad_clip_state_floats();
 int gradnorm_launch(const float* g, int64_t n, float max_norm, float* clip, float* lscale, hipStream_t st);
+// mode-seeking term of one translation direction (modeseek.hip; include/aclgan_hip.h: aclgan_modeseek): a, b = B images of n elements at storage
+// code st (st16.h).  modeseek_part leaves modeseek_scratch_floats(B, n) partials of sum |a - b|; modeseek_grad reads them and the noise rows,
+// writes out4 and the fp32 seeds into da / db (either may be null; both null: out4 only; accumulate bit 0: add to da, bit 1: add to db).  lscale (optional, device): seeds x lscale[0]
+int modeseek_chunks(int64_t n);
+size_t modeseek_scratch_floats(int B, int64_t n);
+int modeseek_part(const void* a, const void* b, int st, int B, int64_t n, float* part, hipStream_t s);
+int modeseek_grad(const void* a, const void* b, int st, int B, int64_t n, const float* part, const float* u, const float* u2, int sd, float u_scale,
+                  float weight, const float* lscale, float* out4, float* da, float* db, int accumulate, hipStream_t s);
 // Adam of a buffer with a clip state: gradnorm_launch, the clipped update (ema / state optional), the scale update under a loss scale
 int adam_flat_clipped(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
                       float* state, int group, float max_norm, float* clip, hipStream_t st);

@@ -223,6 +223,14 @@ struct aclgan_ctx {
     float lecam_lambda = 0.f, lecam_decay = 0.f;
     int lecam_start = 0;
     bool in_dis_update = false;
+    // ---- Mode-seeking regulariser of the generators (aclgan_ctx_set_modeseek; modeseek.hip).  ms_lambda 0: off --
+    // gen_update_impl builds exactly the passes it built before the feature existed.  Otherwise it decodes c_1 / c_2 once more with the noise
+    // rows of ms_z (device memory (2, B, style_dim), read stream-ordered) and seeds the two image pairs' gradients from a tape closure.
+    float ms_lambda = 0.f;
+    const float* ms_z = nullptr;
+    int ms_rows = 0;
+    float* ms_out = nullptr;
+    bool ms_on() const { return ms_lambda > 0.f && ms_z; }
     int carry_arm = ACLGAN_CARRY_OFF;            // what the caller armed for the next update
     int carry_call = ACLGAN_CARRY_OFF;           // mode of the update being built (dry runs: the mode being sized)
     int carry_mode = ACLGAN_CARRY_OFF;           // mode of the pass being built: carry_call inside the two carried passes, OFF elsewhere

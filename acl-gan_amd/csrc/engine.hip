@@ -691,6 +691,19 @@ int aclgan_ctx_set_lecam(aclgan_ctx* ctx, float lambda, float decay, int start, 
     return ACLGAN_OK;
 }
 
+int aclgan_ctx_set_modeseek(aclgan_ctx* ctx, float lambda, const float* z_extra, int rows, float* out8) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(lambda >= 0.f && std::isfinite(lambda), "set_modeseek: lambda = %g is no finite number >= 0", (double)lambda);
+    ACL_REQUIRE(rows >= 0, "set_modeseek: rows = %d", rows);
+    const bool on = lambda > 0.f && z_extra;
+    ACL_REQUIRE(!on || out8, "set_modeseek: lambda > 0 with z_extra needs out8, the eight floats the values are written to");
+    ctx->ms_lambda = on ? lambda : 0.f;
+    ctx->ms_z = on ? z_extra : nullptr;
+    ctx->ms_rows = on ? rows : 0;
+    ctx->ms_out = on ? out8 : nullptr;
+    return ACLGAN_OK;
+}
+
 int aclgan_set_forward_sync(aclgan_ctx* ctx, aclgan_sync_fn fn, void* user, int world_size) {
     ACL_REQUIRE(ctx && world_size >= 1, "bad ctx / world size");
     ctx->sync_fn = fn; ctx->sync_user = user; ctx->sync_world = fn ? world_size : 1;

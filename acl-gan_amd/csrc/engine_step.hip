@@ -73,6 +73,37 @@ static int encode_x_a(aclgan_ctx& c, bool train, int L0, int L1, StepIn* s) {
     return ACLGAN_OK;
 }
 
+// ---- mode-seeking pair of one translation direction (aclgan_ctx_set_modeseek; modeseek.hip) ----
+// img = the direction's translation of x_a as the update built it (decode(content, zu) blended onto x_a); this decodes `content` once more
+// with the noise rows zu2, blends onto x_a into a fresh activation, leaves the partial sums of |img - img2| and pushes the closure that seeds
+// both gradients.  Call it right after img's own blend, BEFORE any consumer of img is built: the closure then runs after every consumer's
+// backward has written img's gradient (x_A_fake is a slice of the joint dis_A batch, whose input gradient OVERWRITES the whole of it -- a seed
+// stored at forward time would be lost) and before either blend's closure reads.  dir: 0 = B (out8[0..3]), 1 = A (out8[4..7]).
+static int modeseek_pair(aclgan_ctx& c, int net, Act* content, Act* zu, Act* zu2, Act* xa, Act* img, int dir) {
+    Act *dec = nullptr, *img2 = nullptr;
+    CHK(decode(c, net, true, content, zu2, &dec)); CHK(c.mark());
+    CHK(zero_grad_of(c, dec));
+    CHK(blend(c, dec, xa, nullptr, &img2, nullptr)); CHK(c.mark());
+    const int B = img->B, sd = zu->H * zu->W * zu->C;
+    const int64_t n = (int64_t)img->H * img->W * img->C;
+    ACL_REQUIRE(img->need_grad && img2->need_grad && img->dt == img2->dt && img->gdt == 0 && img2->gdt == 0, "modeseek: the image pair takes fp32 gradients");
+    float* part = c.allocf((int64_t)modeseek_scratch_floats(B, n));
+    NEED(part);
+    CHK(c.need(img));
+    RUN(modeseek_part(img->d, img2->d, img->dt, B, n, part, c.st));
+    // both images read twice (part, grad); the first image's gradient read and written, the fresh one's written
+    c.count((img->dt ? 2.0 : 4.0) * 4.0 * (double)B * (double)n + 4.0 * 3.0 * (double)B * (double)n);
+    c.push([=](aclgan_ctx& c) -> int {
+        CHK(c.acq(img)); CHK(c.acq(img2));
+        const int acc = (img->written() ? 1 : 0) | (img2->written() ? 2 : 0);
+        RUN(modeseek_grad(img->d, img2->d, img->dt, B, n, part, zu->d, zu2->d, sd, 1.f, c.ms_lambda / (float)B, c.lscale, c.ms_out + 4 * dir, img->g, img2->g,
+                          acc, c.st));
+        mark_written(img); mark_written(img2);
+        return ACLGAN_OK;
+    });
+    return ACLGAN_OK;
+}
+
 // ---- gen_update (trainer.py:99-169, focus branch) ----
 static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, const float* z, int B, int H, int W,
                            const aclgan_hparams& hp, float* L) {
@@ -94,6 +125,14 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     StepIn in;
     auto& [xa, xb, z1, z2, z3, c1, c2] = in;
     CHK(step_inputs(c, x_a, x_b, z, B, H, W, hp.alpha, true, &in));
+    // mode-seeking regulariser: z_4, and alpha z_5 like z_2 (part of the preamble on lane 0)
+    const bool ms = c.ms_on();
+    Act *z4 = nullptr, *z5 = nullptr;
+    if (ms) {
+        const int sd = c.arch.gen_style_dim;
+        CHK(wrap_vec(c, c.ms_z, B, sd, 1.f, &z4));
+        CHK(wrap_vec(c, c.ms_z + (size_t)B * sd, B, sd, hp.alpha, &z5));
+    }
     Act *s2, *c4, *s4, *c3;
     Act *dB4, *dA4, *xB, *xA, *pA1, *rA4, *rB4, *dA24, *xA2, *pA2;
     // joint discriminator inputs: (x_A_fake | x_A2_fake) for dis_A, (pair_A1 | pair_A2) for dis_2
@@ -115,10 +154,13 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     CHK(c.set_lane(L0));
     PASS(decode(c, AB, true, c1, z1, &dB4)); CHK(zero_grad_of(c, dB4));   // trainer.py:108
     PASS(blend(c, dB4, xa, nullptr, &xB, nullptr));                  // trainer.py:110
+    // (the second sample of direction B next to the chain: lane 0 goes on with decode -> encode -> decode of x_A2_fake undisturbed)
+    if (ms) { CHK(c.set_lane(L2)); CHK(modeseek_pair(c, AB, c1, z1, z4, xa, xB, 0)); }
     CHK(c.set_lane(L1));
     PASS(decode(c, BA, true, c2, z2, &dA4)); CHK(zero_grad_of(c, dA4));   // trainer.py:109
     Act *vA1 = c.new_view(jA, 0, B), *vP1 = c.new_view(jP, 0, B), *vA2 = c.new_view(jA, B, B), *vP2 = c.new_view(jP, B, B);
     PASS(blend(c, dA4, xa, xa, &xA, &pA1, vA1, vP1));                // trainer.py:111,132
+    if (ms) CHK(modeseek_pair(c, BA, c2, z2, z5, xa, xA, 1));        // (lane 1, behind the pass whose image it pairs with)
     CHK(c.set_lane(L0));
     PASS(content_encode(c, BA, true, xB, &c3));                      // trainer.py:125
     PASS(decode(c, BA, true, c3, z3, &dA24)); CHK(zero_grad_of(c, dA24)); // trainer.py:127
@@ -416,6 +458,8 @@ static int step_common(aclgan_ctx* ctx, const float* x_a, const float* x_b, cons
         ACL_REQUIRE(ctx->aug_rows == want, "%s at B = %d reads %d augmentation rows (%d B), aclgan_ctx_set_augment was given %d",
                     group_trained == 0 ? "gen_update" : "dis_update", B, want, group_trained == 0 ? 5 : 7, ctx->aug_rows);
     }
+    if (group_trained == 0 && ctx->ms_on())      // (refused here, before anything is enqueued)
+        ACL_REQUIRE(ctx->ms_rows == 2 * B, "gen_update at B = %d reads %d mode-seeking noise rows (2 B: z_4, z_5), aclgan_ctx_set_modeseek was given %d", B, 2 * B, ctx->ms_rows);
     // carried encodings: what the caller armed holds for this call only.  dis_update keeps when armed; gen_update adopts when armed and the
     // record's key is this call's.  Never under stream capture (a graph has no cross-call state), while masks are being recorded (they are
     // logged at forward time), with a fault injected, or with enc_reuse 0.  Whatever happens, the record does not outlive this call.
@@ -434,7 +478,7 @@ static int step_common(aclgan_ctx* ctx, const float* x_a, const float* x_b, cons
     // refused here, before anything is enqueued (the allocator checks every request as well)
     if (check_shape(*ctx, B, H, W) == ACLGAN_OK) {
         for (;;) {
-            const aclgan_ctx::NeedKey key{group_trained, B, H, W, ctx->dtype, tuning_epoch(), sw(SW_DETERMINISTIC), (ctx->bucket_elems > 0 ? 1 : 0) | (carry << 1) | (ctx->aug_policy << 3)};
+            const aclgan_ctx::NeedKey key{group_trained, B, H, W, ctx->dtype, tuning_epoch(), sw(SW_DETERMINISTIC), (ctx->bucket_elems > 0 ? 1 : 0) | (carry << 1) | (ctx->aug_policy << 3) | ((group_trained == 0 && ctx->ms_on() ? 1 : 0) << 6)};
             auto it = ctx->need_cache.find(key);
             if (it == ctx->need_cache.end()) {
                 size_t need = 0;

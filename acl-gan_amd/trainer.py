@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 
 __all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "augment_from_config", "dis_norm_from_config", "draw_augment_params",
-           "ema_from_config", "grad_clip_from_config", "hparams_from_config", "lecam_from_config", "r1_from_config"]
+           "ema_from_config", "grad_clip_from_config", "hparams_from_config", "lecam_from_config", "modeseek_from_config", "r1_from_config"]
 
 DIS_NORMS = ("none", "sn")    # dis.norm values the library implements (sn: SpectralNorm, networks.py:360-361,538-600)
 
@@ -123,6 +123,19 @@ def lecam_from_config(hp):
     return float(lam), float(decay), start
 
 
+def modeseek_from_config(hp):
+    """The mode-seeking regulariser's key (not in the reference; Mao et al. 2019, "Mode Seeking GANs", per image; README / DESIGN.md section 4g):
+    ms_lambda  float >= 0, default 0 = off: no buffer, no library call, the launches and bits of a run without the key.
+    With it gen_update decodes c_1 and c_2 once more with fresh noise and the objective gains ms_lambda * (loss_gen_ms_B + loss_gen_ms_A),
+    ms = mean over the batch of dz / (dI + 1e-5 dz).  The paper uses 1 throughout; nobody has measured which value suits these datasets.
+    It composes with every other key: it never touches the discriminators or the finished gradient buffer.  grad_clip is its companion
+    (the term grows like dz / dI^2 where two samples nearly coincide)."""
+    lam = hp.get("ms_lambda", 0)
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not (0 <= lam and math.isfinite(C.c_float(lam).value)):
+        raise L.AclganError("ms_lambda=%r: expected a finite number >= 0 (0 switches the mode-seeking regulariser off)" % (lam,))
+    return float(lam)
+
+
 def grad_clip_from_config(hp):
     """The gradient-norm keys (not in the reference; torch.nn.utils.clip_grad_norm_ per optimizer group, on the device) as (gen, dis), the
     max_norm of each group, 0 = off:
@@ -146,6 +159,7 @@ def grad_clip_from_config(hp):
 
 
 AUG_SEED_OFFSET = 0x0A06           # the augmentation generator's seed = torch.initial_seed() + rank + this
+MS_SEED_OFFSET = 0x0A07            # the mode-seeking noise generator's seed = torch.initial_seed() + rank + this
 
 
 def draw_augment_params(policy, rows, H, W, generator=None):
@@ -416,6 +430,18 @@ class aclgan_Trainer:
         if self.lecam_lambda > 0:
             self._lecam = torch.zeros(L.lib.aclgan_lecam_state_floats(self._ctx), dtype=torch.float32, device=self.device)
             L.check(L.lib.aclgan_ctx_set_lecam(self._ctx, self.lecam_lambda, self.lecam_decay, self.lecam_start, L.ptr(self._lecam)), "ctx_set_lecam")
+        # mode-seeking regulariser (ms_lambda > 0): z_4, z_5 of an update come from a CPU generator of the trainer's own (seed: initial_seed() +
+        # rank + MS_SEED_OFFSET), so the z and the augmentation rows of a run are the same with and without the key; its state is not part of a
+        # checkpoint.  They are copied into a persistent device tensor per batch size (a replayed graph reads the address it captured) and bound
+        # just before the update (_bind_modeseek); the eight values of an update land in _ms_out.  Off: no tensor, no call
+        self.ms_lambda = modeseek_from_config(hp)
+        self._msgen = None
+        self._ms_dev = {}
+        self._ms_out = torch.zeros(8, dtype=torch.float32, device=self.device) if self.ms_lambda > 0 else None
+        if self.ms_lambda > 0:
+            # on the context before the first workspace query, like the augmentation policy (the two extra passes live in the arena).  rows = 0:
+            # no update accepts this binding, so the placeholder address is never read
+            L.check(L.lib.aclgan_ctx_set_modeseek(self._ctx, self.ms_lambda, L.ptr(self._ms_out), 0, L.ptr(self._ms_out)), "ctx_set_modeseek")
         # the lane scheduler's streams first, before anything else of this process creates one (the rank-0 broadcast below initialises the process
         # group's communicator and its stream): HIP binds streams to hardware queues in creation order (include/aclgan_hip.h, aclgan_warm_streams)
         if os.environ.get("ACLGAN_WARM_STREAMS", "1") not in ("", "0"):
@@ -497,6 +523,8 @@ class aclgan_Trainer:
         self.loss_dis_r1_A = self.loss_dis_r1_B = self.loss_dis_total
         # ... and the LeCam values of the last dis_update, w * mean((D - anchor of the other side)^2) summed per discriminator, without lambda
         self.loss_dis_lecam_A = self.loss_dis_lecam_B = self.loss_dis_lecam_2 = self.loss_dis_total
+        # ... and the mode-seeking values of the last gen_update (without lambda) with the collapse readout mean(dI / dz): it tends to 0 when z is ignored
+        self.loss_gen_ms_A = self.loss_gen_ms_B = self.gen_diversity_A = self.gen_diversity_B = self.loss_dis_total
         self._zgen = None
         # fp16: dynamic loss scaling, state resident on the device (include/aclgan_hip.h: aclgan_bind_loss_scale)
         self._lscale = None
@@ -763,7 +791,26 @@ class aclgan_Trainer:
         L.check(L.lib.aclgan_ctx_set_augment(self._ctx, self.augment, L.ptr(dev), dev.shape[0]), "ctx_set_augment")
         return dev
 
-    def _update(self, which, x_a, x_b, hp, z, aug=None):
+    def _draw_z_ms(self, B):
+        """a fresh draw of this gen_update's (z_4, z_5) from the trainer's own CPU generator"""
+        if self._msgen is None:
+            import torch.distributed as dist
+            rank = dist.get_rank() if self._dist_world() else 0
+            self._msgen = torch.Generator().manual_seed((torch.initial_seed() + rank + MS_SEED_OFFSET) % (1 << 63))
+        return [torch.randn(B, self.style_dim, 1, 1, generator=self._msgen) for _ in range(2)]
+
+    def _bind_modeseek(self, z_ms, B):
+        """This update's (z_4, z_5) into the persistent device tensor of its batch size, which the context reads them from.  Returns that tensor."""
+        if len(z_ms) != 2 or any((not isinstance(t, torch.Tensor)) or t.numel() != B * self.style_dim for t in z_ms):
+            raise L.AclganError("z_ms: expected two (B, gen.style_dim %d, 1, 1) tensors (z_4, z_5) for B = %d" % (self.style_dim, B))
+        dev = self._ms_dev.get(B)
+        if dev is None:
+            dev = self._ms_dev[B] = torch.zeros(2, B, self.style_dim, dtype=torch.float32, device=self.device)
+        dev.copy_(torch.stack([t.reshape(B, self.style_dim).to(torch.float32) for t in z_ms]))
+        L.check(L.lib.aclgan_ctx_set_modeseek(self._ctx, self.ms_lambda, L.ptr(dev), 2 * B, L.ptr(self._ms_out)), "ctx_set_modeseek")
+        return dev
+
+    def _update(self, which, x_a, x_b, hp, z, aug=None, z_ms=None):
         grp = L.GROUP_GEN if which == "gen" else L.GROUP_DIS
         x_a = x_a.to(self.device, torch.float32).contiguous()
         x_b = x_b.to(self.device, torch.float32).contiguous()
@@ -774,6 +821,11 @@ class aclgan_Trainer:
             raise L.AclganError("aug given, but this trainer was built without dis_augment")
         if self.augment and aug is None:      # (host work: before the copies below, which wait for the device)
             aug = self._draw_augment(which, B, H, W)
+        ms = which == "gen" and self.ms_lambda > 0
+        if z_ms is not None and not ms:
+            raise L.AclganError("z_ms given, but this is no gen_update of a trainer built with ms_lambda > 0")
+        if ms and z_ms is None:
+            z_ms = self._draw_z_ms(B)
         if z is None:
             z = self._draw_z(B)
         if any(t.numel() != B * self.style_dim for t in z):      # (refused here, by name, before anything is copied or enqueued)
@@ -783,6 +835,7 @@ class aclgan_Trainer:
         hpc = hparams_from_config(hp)
         with torch.cuda.device(self.device):
             aug_dev = self._bind_augment(which, aug) if self.augment else None
+            ms_dev = self._bind_modeseek(z_ms, B) if ms else None
             det_now = bool(L.lib.aclgan_get_deterministic())
             if det_now != self.deterministic:      # the process-wide mode changed under us: scratch sizes depend on it
                 self.deterministic = det_now
@@ -796,7 +849,7 @@ class aclgan_Trainer:
             fn = L.lib.aclgan_gen_update if which == "gen" else L.lib.aclgan_dis_update
             # lazy R1: on the discriminator updates whose count BEFORE the update is a multiple of r1_every (the count is saved and resumed)
             r1 = which == "dis" and self.r1_gamma > 0 and self._opt[grp]["steps"] % self.r1_every == 0
-            if self.hip_graph and self._reducer is None and self._run_graph(which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev):
+            if self.hip_graph and self._reducer is None and self._run_graph(which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev, ms_dev):
                 # zero_grad + update replayed from the captured graph; the pass is not captured: eagerly after it, before Adam
                 if r1:
                     self._r1_pass(x_a, x_b, B, H, W, st)
@@ -835,6 +888,9 @@ class aclgan_Trainer:
             setattr(self, "grad_norm_gen" if which == "gen" else "grad_norm_dis", self._clip[grp][0].clone())
         if which == "gen":
             self._publish_losses(0, 12)
+            if ms:      # fresh 0-d tensors per update, like the losses
+                vals = self._ms_out.clone()
+                self.loss_gen_ms_B, self.gen_diversity_B, self.loss_gen_ms_A, self.gen_diversity_A = vals[0], vals[1], vals[4], vals[5]
         else:
             self._publish_losses(12, 16)
             if self._lecam is not None:
@@ -865,7 +921,7 @@ class aclgan_Trainer:
         self.loss_dis_r1_A, self.loss_dis_r1_B = vals[0], vals[1]
 
     # ---- HIP-graph replay of an update (opt-in, see __init__) ----
-    def _run_graph(self, which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev=None):
+    def _run_graph(self, which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev=None, ms_dev=None):
         """True: the update ran as a graph replay.  False: run it eagerly (first call of a new key -- it also performs the
         library's one-time initialisation outside any capture -- or capture is unavailable)."""
         key = (B, H, W, bytes(hpc), self._ws.data_ptr(), self._ws.numel(), self.compute_dtype, self.deterministic)
@@ -873,6 +929,8 @@ class aclgan_Trainer:
             key += (self.augment, aug_dev.data_ptr(), aug_dev.shape[0])
         if self._lecam is not None:      # (lambda, decay and start are kernel arguments of the captured launches, the state's address too)
             key += (self.lecam_lambda, self.lecam_decay, self.lecam_start, self._lecam.data_ptr())
+        if ms_dev is not None:      # (lambda is a kernel argument of the captured launches; the noise rows are refilled before every replay)
+            key += (self.ms_lambda, ms_dev.data_ptr(), self._ms_out.data_ptr())
         ent = self._graphs.get(which)
         if ent is None or ent["key"] != key:
             self._graphs[which] = {"key": key, "graph": None}
@@ -986,9 +1044,15 @@ class aclgan_Trainer:
         return v
 
     # ---- the hot path (trainer.py:90-170, 247-293) ----
-    def gen_update(self, x_a, x_b, hyperparameters, z=None, aug=None):
-        """aug (tests): this update's (5 B, 8) augmentation rows instead of a draw (dis_augment; include/aclgan_hip.h: aclgan_ctx_set_augment)"""
-        self._update("gen", x_a, x_b, hyperparameters, z, aug)
+    def gen_update(self, x_a, x_b, hyperparameters, z=None, aug=None, z_ms=None):
+        """aug (tests): this update's (5 B, 8) augmentation rows instead of a draw (dis_augment; include/aclgan_hip.h: aclgan_ctx_set_augment);
+        z_ms (tests): this update's (z_4, z_5) instead of a draw (ms_lambda; include/aclgan_hip.h: aclgan_ctx_set_modeseek)"""
+        self._update("gen", x_a, x_b, hyperparameters, z, aug, z_ms)
+
+    def modeseek_log_text(self):
+        """train.py's log-line suffix: the two mode-seeking values of the last gen_update and the two collapse readouts"""
+        return " ms_A=%.4g ms_B=%.4g div_A=%.4g div_B=%.4g" % (float(self.loss_gen_ms_A), float(self.loss_gen_ms_B), float(self.gen_diversity_A),
+                                                               float(self.gen_diversity_B))
 
     def dis_update(self, x_a, x_b, hyperparameters, z=None, aug=None):
         """aug (tests): this update's (7 B, 8) augmentation rows instead of a draw"""

@@ -309,6 +309,41 @@ int aclgan_ctx_set_augment(aclgan_ctx* ctx, int policy, const float* params, int
  * and needs no GPU (0 for a null context); aclgan_step_algorithmic_bytes counts the fold while a state is bound. */
 size_t aclgan_lecam_state_floats(aclgan_ctx* ctx);
 int aclgan_ctx_set_lecam(aclgan_ctx* ctx, float lambda, float decay, int start, float* state);
+/* Mode-seeking regulariser of the generators (NOT in the reference; Mao et al., CVPR 2019, "Mode Seeking GANs for Diverse Image Synthesis";
+ * DESIGN.md section 4g).  Only aclgan_gen_update changes.  With lambda > 0 it reads two more noise tensors z_4, z_5 of shape (B, style_dim) and
+ * runs two more decoder passes on the content codes it already has:
+ *     I'_B = focus_translation(gen_AB.decode(c_1, z_4)[:, :3], x_a, mask)        paired with I_B = x_B_fake,  u = z_1,       u' = z_4
+ *     I'_A = focus_translation(gen_BA.decode(c_2, alpha z_5)[:, :3], x_a, mask)  paired with I_A = x_A_fake,  u = alpha z_2, u' = alpha z_5
+ * (focus_loss 0 with gen.output_dim 3: the decoder output is the image).  The extra images go to no discriminator, get no focus loss and take
+ * no augmentation.  Per image b and direction, with N = 3 H W:
+ *     dI_b = (1/N) sum_p |I[b,p] - I'[b,p]|          dz_b = (1/style_dim) sum_k |u[b,k] - u'[b,k]|
+ *     ms_b = dz_b / (dI_b + eps * dz_b),  eps = 1e-5  (0 where dz_b == 0)
+ *     loss_gen_ms_D = (1/B) sum_b ms_b               div_D = (1/B) sum_b (dI_b / dz_b, or 0 where dz_b == 0)
+ * The objective gains lambda * (loss_gen_ms_B + loss_gen_ms_A); per image, so that data-parallel ranks on equal shards average to the joint
+ * batch without a forward sync.  Gradient seeds, S the live fp16 loss scale or 1, sign(0) = 0:
+ *     dL/dI [b,p] = -S * (lambda / B) * dz_b / (dI_b + eps dz_b)^2 * sign(I[b,p] - I'[b,p]) / N          dL/dI'[b,p] = -dL/dI[b,p]
+ * From there the update's own backward carries them through the blends, both decodes, the MLPs and into c_1 / c_2 and the content encoders;
+ * x_a and the style encoders receive nothing.  The term grows like dz / dI^2 where two samples nearly coincide: aclgan_bind_grad_clip is
+ * its companion.  ACLGAN_L_GEN_TOTAL and the 16 loss slots keep their meaning and values; the new values live in out8 only.
+ *
+ * aclgan_modeseek is the fp32 operator of one direction on caller-supplied tensors: a, b = I, I' as B images of n_per_image floats; u, u2 =
+ * (B, style_dim) noise rows, dz multiplied by |u_scale|; weight = lambda / B; loss_scale NULL or a device float (S).  out4 (device) =
+ * loss_gen_ms, div, 0, 0 (two reserved).  da / db receive dL/da, dL/db (accumulate != 0: are added to); either may be NULL, both NULL is
+ * monitoring only.  No pointer needs 16-byte alignment (4 is enough); a, b, da, db that reach a 16-byte boundary together are streamed with
+ * 16-byte accesses.  scratch: aclgan_modeseek_scratch_bytes(B, n_per_image) bytes -- one partial per (image, chunk), chunks per image =
+ * min(128, max(1, ceil((n_per_image / 4) / 512))).  Two launches, no atomics: the same bits run to run.
+ *
+ * aclgan_ctx_set_modeseek: z_extra is DEVICE memory (2, B, style_dim) = z_4, z_5 and out8 DEVICE memory of 8 floats, [0..3] = out4 of
+ * direction B, [4..7] = out4 of direction A; both pointers are kept, not the contents (read / written stream-ordered by the gen_updates that
+ * follow, also under a captured graph).  rows must be 2 B of the update that follows, else that update returns ACLGAN_EINVAL and launches
+ * nothing.  lambda == 0 or z_extra == NULL switches the feature off (a context's default: the launches, buffers and bits of a context that
+ * never heard of it).  ACLGAN_EINVAL, with nothing enqueued, for a negative or non-finite lambda, for rows < 0, and for lambda > 0 with z_extra
+ * but no out8.  The launch-free queries (aclgan_workspace_bytes, aclgan_step_algorithmic_bytes, aclgan_step_executed_flops) account for the
+ * two passes and the four launches while the feature is on, whatever rows says. */
+size_t aclgan_modeseek_scratch_bytes(int B, int64_t n_per_image);
+int aclgan_modeseek(const float* a, const float* b, int B, int64_t n_per_image, const float* u, const float* u2, int style_dim, float u_scale,
+                    float weight, const float* loss_scale, float* out4, float* da, float* db, int accumulate, void* scratch, void* stream);
+int aclgan_ctx_set_modeseek(aclgan_ctx* ctx, float lambda, const float* z_extra, int rows, float* out8);
 /* arena for ONE forward-only call below (encode / decode / discriminator forward) on (B,*,H,W) images: what
  * test.py:55-131 and trainer.sample need -- far smaller than a training step's, and without its shape constraints
  * (any H, W the networks accept, e.g. the 256x340 a Resize(256) of a non-square photo yields) */

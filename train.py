@@ -170,7 +170,9 @@ def main():
                   # (lecam_lambda > 0: the regulariser's values of the last dis_update and the first scale's anchors, mean D on real / on fake)
                   (trainer.lecam_log_text() if trainer.lecam_lambda > 0 else "") +
                   # (grad_clip* on: the gradient norms of the last generator / discriminator update and the updates skipped for a non-finite norm)
-                  (trainer.grad_clip_log_text() if max(trainer.grad_clip) > 0 else ""))
+                  (trainer.grad_clip_log_text() if max(trainer.grad_clip) > 0 else "") +
+                  # (ms_lambda > 0: the mode-seeking values of the last gen_update and div = mean(dI / dz), which tends to 0 when z is ignored)
+                  (trainer.modeseek_log_text() if trainer.ms_lambda > 0 else ""))
             loss_log.append(iterations + 1, vals.tolist())
         if display is not None and image_due(iterations, config, "image_save_iter"):      # train.py:83-90
             train_a, train_b, test_a, test_b = display
