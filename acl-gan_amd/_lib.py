@@ -150,6 +150,11 @@ SIGNATURES = {
     "aclgan_modeseek_scratch_bytes": (sz, [ci, i64]),
     "aclgan_modeseek": (ci, [vp, vp, ci, i64, vp, vp, ci, cf, cf, vp, vp, vp, vp, ci, vp, vp]),
     "aclgan_ctx_set_modeseek": (ci, [vp, cf, vp, ci, vp]),
+    "aclgan_ada_state_floats": (sz, []),
+    "aclgan_ctx_set_ada": (ci, [vp, vp, cf, ci, cf]),
+    "aclgan_augment_gate": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+    "aclgan_ada_sign_multi": (ci, [vp, vp, vp, ci, vp, vp]),
+    "aclgan_ada_fold": (ci, [vp, cf, ci, cf, vp]),
     "aclgan_lsgan_lecam_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, ci, vp, vp, vp]),
     "aclgan_lecam_fold": (ci, [vp, ci, cf, vp]),
     "aclgan_diffaugment_scratch_bytes": (sz, [ci, ci, ci, ci]),

@@ -402,6 +402,25 @@ int aclgan_lsgan_lecam_multi(const float* const* o, const int* n, const float* t
     }
     return lsgan_lecam_batch(t.data(), nterms, lambda, start, count, (hipStream_t)stream, lscale);
 }
+int aclgan_augment_gate(const float* rows, const float* u, const float* state, int n, int H, int W, int policy, float* rows_eff, void* stream) {
+    return augment_gate(rows, u, state, n, H, W, policy, rows_eff, (hipStream_t)stream);
+}
+int aclgan_ada_sign_multi(const float* const* o, const int* n, const float* weight, int nterms, float* acc, void* stream) {
+    ACL_REQUIRE(o && n && weight && acc && nterms >= 1 && nterms <= 1024, "ada_sign_multi: bad arguments");
+    std::vector<AdaSignTerm> t(nterms);
+    for (int i = 0; i < nterms; ++i) {
+        ACL_REQUIRE(o[i] && n[i] > 0 && std::isfinite(weight[i]) && weight[i] >= 0.f, "ada_sign_multi: bad term %d", i);
+        t[i] = AdaSignTerm{o[i], n[i], weight[i]};
+    }
+    return ada_sign(t.data(), nterms, acc, (hipStream_t)stream);
+}
+int aclgan_ada_fold(float* state, float target, int interval, float step, void* stream) {
+    ACL_REQUIRE(state, "ada_fold: null state");
+    ACL_REQUIRE(target >= -1.f && target <= 1.f, "ada_fold: target = %g lies outside [-1, 1]", (double)target);
+    ACL_REQUIRE(interval >= 1, "ada_fold: interval = %d is no integer >= 1", interval);
+    ACL_REQUIRE(step >= 0.f && std::isfinite(step), "ada_fold: step = %g is no finite number >= 0", (double)step);
+    return ada_fold(state, target, interval, step, (hipStream_t)stream);
+}
 int aclgan_lecam_fold(float* state, int num_scales, float decay, void* stream) {
     ACL_REQUIRE(state && num_scales >= 1, "lecam_fold: bad arguments");
     ACL_REQUIRE(decay >= 0.f && decay < 1.f, "lecam_fold: decay = %g lies outside [0, 1)", (double)decay);

@@ -300,6 +300,16 @@ int lsgan_lecam_batch(const LecamTerm* terms, int nterms, float lambda, int star
 static inline size_t lecam_state_floats(int S) { return (size_t)18 * S + 4; }
 // anchors <- the update's weighted means (copy at count 0, else decay*a + (1-decay)*m; a non-finite m is skipped), sums <- 0, count += 1
 int lecam_fold(float* state, int num_scales, float decay, hipStream_t st);
+// adaptive augmentation probability (ada.hip; include/aclgan_hip.h: aclgan_ctx_set_ada).  augment_gate: rows_eff[r] = rows[r] where
+// u[r][k] < state[0] for operation k of the policy, else the operation's neutral columns.  ada_sign: acc[0] += w mean(sgn(o - 0.5)), acc[1] += w
+// per term, in index order.  ada_fold: the update's r into the interval, p moved every `interval` updates, the per-update pairs zeroed.
+struct AdaSignTerm { const float* o; int n; float weight; };
+const int ADA_SIGN_MAX_TERMS = 12;
+// state layout: p | r_t | interval sum | interval count | updates (int32) | adjustments (int32) | r | 0 | (sum w q, sum w) of dis_A | of dis_B
+static inline size_t ada_state_floats() { return 12; }
+int augment_gate(const float* rows, const float* u, const float* state, int n, int H, int W, int policy, float* rows_eff, hipStream_t st);
+int ada_sign(const AdaSignTerm* terms, int nterms, float* acc, hipStream_t st);
+int ada_fold(float* state, float target, int interval, float step, hipStream_t st);
 // L1 (trainer.py:61-62): loss_slot = mean|a[..,:3] - b|; a has a_stride channels (4: decoder output), b 3 channels.
 const int L1_PART_FLOATS = 1024;
 int l1_loss(const float* a, int a_stride, const float* b, int64_t npix, float* loss_slot, float* d_a, float gscale, int d_accumulate, hipStream_t st,

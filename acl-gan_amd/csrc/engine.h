@@ -223,6 +223,12 @@ struct aclgan_ctx {
     float lecam_lambda = 0.f, lecam_decay = 0.f;
     int lecam_start = 0;
     bool in_dis_update = false;
+    // ---- Adaptive augmentation probability (aclgan_ctx_set_ada; ada.hip).  ada_state null: off -- dis_lsgan and
+    // dis_update_impl build exactly the launches they built before the feature existed.  Otherwise the train passes of dis_A and dis_B that
+    // dis_update_impl builds add the sign statistic of their real-side terms to their pair of the state, and the update ends with the fold.
+    float* ada_state = nullptr;
+    float ada_target = 0.f, ada_step = 0.f;
+    int ada_interval = 1;
     // ---- Mode-seeking regulariser of the generators (aclgan_ctx_set_modeseek; modeseek.hip).  ms_lambda 0: off --
     // gen_update_impl builds exactly the passes it built before the feature existed.  Otherwise it decodes c_1 / c_2 once more with the noise
     // rows of ms_z (device memory (2, B, style_dim), read stream-ordered) and seeds the two image pairs' gradients from a tape closure.

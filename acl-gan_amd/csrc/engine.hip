@@ -691,6 +691,17 @@ int aclgan_ctx_set_lecam(aclgan_ctx* ctx, float lambda, float decay, int start, 
     return ACLGAN_OK;
 }
 
+size_t aclgan_ada_state_floats(void) { return ada_state_floats(); }
+int aclgan_ctx_set_ada(aclgan_ctx* ctx, float* state, float target, int interval, float step) {
+    ACL_REQUIRE(ctx, "null ctx");
+    ACL_REQUIRE(target >= -1.f && target <= 1.f, "set_ada: target = %g lies outside [-1, 1]", (double)target);
+    ACL_REQUIRE(interval >= 1, "set_ada: interval = %d is no integer >= 1", interval);
+    ACL_REQUIRE(step >= 0.f && std::isfinite(step), "set_ada: step = %g is no finite number >= 0", (double)step);
+    ctx->ada_state = state;      // (NULL: off)
+    ctx->ada_target = state ? target : 0.f; ctx->ada_interval = state ? interval : 1; ctx->ada_step = state ? step : 0.f;
+    return ACLGAN_OK;
+}
+
 int aclgan_ctx_set_modeseek(aclgan_ctx* ctx, float lambda, const float* z_extra, int rows, float* out8) {
     ACL_REQUIRE(ctx, "null ctx");
     ACL_REQUIRE(lambda >= 0.f && std::isfinite(lambda), "set_modeseek: lambda = %g is no finite number >= 0", (double)lambda);

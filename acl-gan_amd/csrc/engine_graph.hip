@@ -720,9 +720,19 @@ int dis_lsgan(aclgan_ctx& c, int net, bool train, Act* x, int nb, int row0, cons
             lt[j].stats = st + 6 * S + ((D * S + s) * 2 + k) * 2;
         }
         RUN(lsgan_lecam_batch(lt.data(), (int)lt.size(), c.lecam_lambda, c.lecam_start, reinterpret_cast<const int*>(st + 18 * S + 3), c.st, c.lscale));
-        return ACLGAN_OK;
+    } else RUN(lsgan_loss_batch(terms.data(), (int)terms.size(), c.st, c.lscale));
+    if (train && c.in_dis_update && c.ada_state && net != ACLGAN_NET_DIS_2) {
+        // overfitting signal (ada.hip): the real-side terms (target 1: x_a, x_b) of this pass, one launch behind the loss kernel on its lane.
+        // dis_2 has no real side: both of its inputs are generated.  A pass without such a term (the fake-side calls under spectral norm) launches nothing.
+        std::vector<AdaSignTerm> at;
+        double bytes = 0.0;
+        for (const LsganTerm& t : terms)
+            if (t.target == 1.f) { at.push_back(AdaSignTerm{t.o, t.n, t.weight}); bytes += 4.0 * (double)t.n; }
+        if (!at.empty()) {
+            c.count(bytes + 2.0 * 4.0 * 2.0);
+            RUN(ada_sign(at.data(), (int)at.size(), c.ada_state + 8 + 2 * (net - ACLGAN_NET_DIS_A), c.st));
+        }
     }
-    RUN(lsgan_loss_batch(terms.data(), (int)terms.size(), c.st, c.lscale));
     return ACLGAN_OK;
 }
 

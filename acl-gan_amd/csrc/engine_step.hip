@@ -321,6 +321,10 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
         c.count(2.0 * 4.0 * (double)lecam_state_floats(c.arch.dis_num_scales));
         RUN(lecam_fold(c.lecam_state, c.arch.dis_num_scales, c.lecam_decay, c.st));
     }
+    if (c.ada_state) {        // every sign launch lies before the join: r of this update into the interval, p moves for the NEXT update's gate
+        c.count(2.0 * 4.0 * (double)ada_state_floats());
+        RUN(ada_fold(c.ada_state, c.ada_target, c.ada_interval, c.ada_step, c.st));
+    }
     return run_tape(c);   // loss_dis_total.backward() (trainer.py:292)
 }
 #undef PASS

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "arch_from_config", "augment_from_config", "dis_norm_from_config", "draw_augment_params",
+__all__ = ["aclgan_Trainer", "AdaINGen", "MsImageDis", "ada_from_config", "arch_from_config", "augment_from_config", "dis_norm_from_config", "draw_augment_params",
            "ema_from_config", "grad_clip_from_config", "hparams_from_config", "lecam_from_config", "modeseek_from_config", "r1_from_config"]
 
 DIS_NORMS = ("none", "sn")    # dis.norm values the library implements (sn: SpectralNorm, networks.py:360-361,538-600)
@@ -123,6 +123,38 @@ def lecam_from_config(hp):
     return float(lam), float(decay), start
 
 
+def ada_from_config(hp):
+    """The adaptive-augmentation keys (not in the reference; Karras et al. 2020, "Training GANs with Limited Data", ADA; README / DESIGN.md
+    section 4h) as None (dis_augment_p absent: no buffer, no library call, the launches and bits of a run without the keys) or
+    (p0, adaptive, target, interval, kimg):
+    dis_augment_p  a number in [0, 1]: every operation of dis_augment is applied to a discriminator input with that fixed probability, and the
+                   overfitting signal r is monitored; or the string adaptive: p starts at 0 and is steered towards r = ada_target.
+                   It needs a non-empty dis_augment.
+    ada_target     number in [-1, 1], default 0.6     |
+    ada_interval   int >= 1, default 4 dis updates    |  read only with adaptive (a fixed p closes its monitoring intervals at the defaults)
+    ada_kimg       number > 0, default 500            |  p moves by ada_interval * B / (ada_kimg * 1000) per interval
+    The three defaults are ADA's; nobody has measured which values suit these datasets (README)."""
+    if "dis_augment_p" not in hp:
+        return None
+    v = hp["dis_augment_p"]
+    adaptive = isinstance(v, str) and v.strip() == "adaptive"
+    if not adaptive and (isinstance(v, bool) or not isinstance(v, (int, float)) or not (0 <= v <= 1)):
+        raise L.AclganError("dis_augment_p=%r: expected a number in [0, 1] or the string adaptive" % (v,))
+    if not augment_from_config(hp):
+        raise L.AclganError("dis_augment_p=%r needs a non-empty dis_augment (a comma-separated subset of %s): there is nothing to apply with "
+                            "that probability" % (v, ",".join(L.AUG)))
+    target, interval, kimg = 0.6, 4, 500.0
+    if adaptive:
+        target, interval, kimg = hp.get("ada_target", target), hp.get("ada_interval", interval), hp.get("ada_kimg", kimg)
+        if isinstance(target, bool) or not isinstance(target, (int, float)) or not (-1 <= target <= 1):
+            raise L.AclganError("ada_target=%r: expected a number in [-1, 1]" % (target,))
+        if isinstance(interval, bool) or not isinstance(interval, int) or not 1 <= interval < 2 ** 31:
+            raise L.AclganError("ada_interval=%r: expected an integer >= 1 (below 2**31)" % (interval,))
+        if isinstance(kimg, bool) or not isinstance(kimg, (int, float)) or not (kimg > 0 and math.isfinite(C.c_float(kimg).value)):
+            raise L.AclganError("ada_kimg=%r: expected a finite number > 0" % (kimg,))
+    return (0.0 if adaptive else float(v)), adaptive, float(target), interval, float(kimg)
+
+
 def modeseek_from_config(hp):
     """The mode-seeking regulariser's key (not in the reference; Mao et al. 2019, "Mode Seeking GANs", per image; README / DESIGN.md section 4g):
     ms_lambda  float >= 0, default 0 = off: no buffer, no library call, the launches and bits of a run without the key.
@@ -160,6 +192,7 @@ def grad_clip_from_config(hp):
 
 AUG_SEED_OFFSET = 0x0A06           # the augmentation generator's seed = torch.initial_seed() + rank + this
 MS_SEED_OFFSET = 0x0A07            # the mode-seeking noise generator's seed = torch.initial_seed() + rank + this
+ADA_SEED_OFFSET = 0x0A08           # the gate's uniforms' generator's seed = torch.initial_seed() + rank + this
 
 
 def draw_augment_params(policy, rows, H, W, generator=None):
@@ -430,6 +463,18 @@ class aclgan_Trainer:
         if self.lecam_lambda > 0:
             self._lecam = torch.zeros(L.lib.aclgan_lecam_state_floats(self._ctx), dtype=torch.float32, device=self.device)
             L.check(L.lib.aclgan_ctx_set_lecam(self._ctx, self.lecam_lambda, self.lecam_decay, self.lecam_start, L.ptr(self._lecam)), "ctx_set_lecam")
+        # adaptive augmentation probability (dis_augment_p): p, the overfitting signal and the controller's counters in ONE persistent device
+        # tensor (include/aclgan_hip.h: aclgan_ctx_set_ada) that the gate reads before an update and dis_update folds -- no host synchronisation,
+        # a replayed graph included.  The gate's uniforms come from a third CPU generator of the trainer's own (seed: initial_seed() + rank +
+        # ADA_SEED_OFFSET), so the augmentation rows and the z of a run are the same with and without the key; its state is not part of a
+        # checkpoint.  The context is given the controller's parameters before every update (_bind_ada: the step depends on the batch size)
+        self.ada = ada_from_config(hp)
+        self._ada = self._adagen = None
+        self._ada_dev = {}
+        self._ada_bound = None
+        if self.ada is not None:
+            self._ada = torch.zeros(L.lib.aclgan_ada_state_floats(), dtype=torch.float32, device=self.device)
+            self._ada[0] = self.ada[0]
         # mode-seeking regulariser (ms_lambda > 0): z_4, z_5 of an update come from a CPU generator of the trainer's own (seed: initial_seed() +
         # rank + MS_SEED_OFFSET), so the z and the augmentation rows of a run are the same with and without the key; its state is not part of a
         # checkpoint.  They are copied into a persistent device tensor per batch size (a replayed graph reads the address it captured) and bound
@@ -791,6 +836,40 @@ class aclgan_Trainer:
         L.check(L.lib.aclgan_ctx_set_augment(self._ctx, self.augment, L.ptr(dev), dev.shape[0]), "ctx_set_augment")
         return dev
 
+    def _draw_aug_u(self, rows):
+        """a fresh draw of this update's gate uniforms, (rows, 4) in [0, 1) (column 3 unused), from the trainer's third CPU generator"""
+        if self._adagen is None:
+            import torch.distributed as dist
+            rank = dist.get_rank() if self._dist_world() else 0
+            self._adagen = torch.Generator().manual_seed((torch.initial_seed() + rank + ADA_SEED_OFFSET) % (1 << 63))
+        return torch.rand(rows, 4, generator=self._adagen)
+
+    def _bind_ada(self, B):
+        """The controller's parameters onto the context: step = ada_interval * B / (ada_kimg * 1000) with B this update's (per-rank) batch,
+        0 for a fixed p.  Returns what a captured graph holds as kernel arguments."""
+        _, adaptive, target, interval, kimg = self.ada
+        step = interval * B / (kimg * 1000.0) if adaptive else 0.0
+        key = (self._ada.data_ptr(), target, interval, step)
+        if key != self._ada_bound:
+            L.check(L.lib.aclgan_ctx_set_ada(self._ctx, L.ptr(self._ada), target, interval, step), "ctx_set_ada")
+            self._ada_bound = key
+        return key
+
+    def _gate_augment(self, which, aug_dev, aug_u, H, W):
+        """The gate (aclgan_augment_gate), eagerly on the update's stream: this update's rows and uniforms and the p of the moment, read on the
+        device, into the persistent effective rows of (update, row count), which the context then reads instead of the rows.  Returns that tensor."""
+        rows = aug_dev.shape[0]
+        key = (which, rows)
+        ent = self._ada_dev.get(key)
+        if ent is None:
+            ent = self._ada_dev[key] = (torch.zeros(rows, 4, dtype=torch.float32, device=self.device),
+                                        torch.zeros(rows, 8, dtype=torch.float32, device=self.device))
+        u_dev, eff = ent
+        u_dev.copy_(aug_u.to(torch.float32))
+        L.check(L.lib.aclgan_augment_gate(L.ptr(aug_dev), L.ptr(u_dev), L.ptr(self._ada), rows, H, W, self.augment, L.ptr(eff), self._st()), "augment_gate")
+        L.check(L.lib.aclgan_ctx_set_augment(self._ctx, self.augment, L.ptr(eff), rows), "ctx_set_augment")
+        return eff
+
     def _draw_z_ms(self, B):
         """a fresh draw of this gen_update's (z_4, z_5) from the trainer's own CPU generator"""
         if self._msgen is None:
@@ -810,7 +889,7 @@ class aclgan_Trainer:
         L.check(L.lib.aclgan_ctx_set_modeseek(self._ctx, self.ms_lambda, L.ptr(dev), 2 * B, L.ptr(self._ms_out)), "ctx_set_modeseek")
         return dev
 
-    def _update(self, which, x_a, x_b, hp, z, aug=None, z_ms=None):
+    def _update(self, which, x_a, x_b, hp, z, aug=None, z_ms=None, aug_u=None):
         grp = L.GROUP_GEN if which == "gen" else L.GROUP_DIS
         x_a = x_a.to(self.device, torch.float32).contiguous()
         x_b = x_b.to(self.device, torch.float32).contiguous()
@@ -819,8 +898,16 @@ class aclgan_Trainer:
             raise L.AclganError("x_a / x_b must both be (B,3,H,W); got %s and %s" % (tuple(x_a.shape), tuple(x_b.shape)))
         if aug is not None and not self.augment:
             raise L.AclganError("aug given, but this trainer was built without dis_augment")
+        if aug_u is not None:      # (refused here, before a generator moves or anything is copied)
+            if self._ada is None:
+                raise L.AclganError("aug_u given, but this trainer was built without dis_augment_p")
+            rows = aug.shape[0] if isinstance(aug, torch.Tensor) and aug.dim() == 2 else (5 if which == "gen" else 7) * B
+            if not (isinstance(aug_u, torch.Tensor) and tuple(aug_u.shape) == (rows, 4)):
+                raise L.AclganError("aug_u: expected a (%d, 4) tensor of uniforms in [0, 1), one row per augmentation row" % rows)
         if self.augment and aug is None:      # (host work: before the copies below, which wait for the device)
             aug = self._draw_augment(which, B, H, W)
+        if self._ada is not None and aug_u is None:
+            aug_u = self._draw_aug_u((5 if which == "gen" else 7) * B)
         ms = which == "gen" and self.ms_lambda > 0
         if z_ms is not None and not ms:
             raise L.AclganError("z_ms given, but this is no gen_update of a trainer built with ms_lambda > 0")
@@ -835,6 +922,10 @@ class aclgan_Trainer:
         hpc = hparams_from_config(hp)
         with torch.cuda.device(self.device):
             aug_dev = self._bind_augment(which, aug) if self.augment else None
+            ada_key = None
+            if self._ada is not None:      # p of the moment onto this update's rows, before the update (under hip_graph: before the replay)
+                ada_key = self._bind_ada(B)
+                aug_dev = self._gate_augment(which, aug_dev, aug_u, H, W)
             ms_dev = self._bind_modeseek(z_ms, B) if ms else None
             det_now = bool(L.lib.aclgan_get_deterministic())
             if det_now != self.deterministic:      # the process-wide mode changed under us: scratch sizes depend on it
@@ -849,7 +940,7 @@ class aclgan_Trainer:
             fn = L.lib.aclgan_gen_update if which == "gen" else L.lib.aclgan_dis_update
             # lazy R1: on the discriminator updates whose count BEFORE the update is a multiple of r1_every (the count is saved and resumed)
             r1 = which == "dis" and self.r1_gamma > 0 and self._opt[grp]["steps"] % self.r1_every == 0
-            if self.hip_graph and self._reducer is None and self._run_graph(which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev, ms_dev):
+            if self.hip_graph and self._reducer is None and self._run_graph(which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev, ms_dev, ada_key):
                 # zero_grad + update replayed from the captured graph; the pass is not captured: eagerly after it, before Adam
                 if r1:
                     self._r1_pass(x_a, x_b, B, H, W, st)
@@ -921,7 +1012,7 @@ class aclgan_Trainer:
         self.loss_dis_r1_A, self.loss_dis_r1_B = vals[0], vals[1]
 
     # ---- HIP-graph replay of an update (opt-in, see __init__) ----
-    def _run_graph(self, which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev=None, ms_dev=None):
+    def _run_graph(self, which, grp, fn, x_a, x_b, zz, B, H, W, hpc, aug_dev=None, ms_dev=None, ada_key=None):
         """True: the update ran as a graph replay.  False: run it eagerly (first call of a new key -- it also performs the
         library's one-time initialisation outside any capture -- or capture is unavailable)."""
         key = (B, H, W, bytes(hpc), self._ws.data_ptr(), self._ws.numel(), self.compute_dtype, self.deterministic)
@@ -931,6 +1022,8 @@ class aclgan_Trainer:
             key += (self.lecam_lambda, self.lecam_decay, self.lecam_start, self._lecam.data_ptr())
         if ms_dev is not None:      # (lambda is a kernel argument of the captured launches; the noise rows are refilled before every replay)
             key += (self.ms_lambda, ms_dev.data_ptr(), self._ms_out.data_ptr())
+        if ada_key is not None:     # (the state's address, target, interval and step are kernel arguments of the captured sign and fold launches)
+            key += ada_key
         ent = self._graphs.get(which)
         if ent is None or ent["key"] != key:
             self._graphs[which] = {"key": key, "graph": None}
@@ -986,6 +1079,10 @@ class aclgan_Trainer:
             # LeCam anchors: every rank starts from rank 0's (here and after resume()), then keeps its own -- each rank sees its own shard,
             # the anchors are not all-reduced; the parameter gradients are, as before
             broadcast_flat(self._lecam)
+        if self._ada is not None:
+            # p and the controller's counters: every rank starts from rank 0's (here and after resume()), then keeps its own -- each rank
+            # steers by the signal of its own shard, which is not all-reduced: the ranks may drift apart in p
+            broadcast_flat(self._ada)
         steps = torch.tensor([self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls], dtype=torch.int64, device=self.device)
         dist.broadcast(steps, 0)
         self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls = (int(v) for v in steps.tolist())
@@ -1044,19 +1141,36 @@ class aclgan_Trainer:
         return v
 
     # ---- the hot path (trainer.py:90-170, 247-293) ----
-    def gen_update(self, x_a, x_b, hyperparameters, z=None, aug=None, z_ms=None):
+    def gen_update(self, x_a, x_b, hyperparameters, z=None, aug=None, z_ms=None, aug_u=None):
         """aug (tests): this update's (5 B, 8) augmentation rows instead of a draw (dis_augment; include/aclgan_hip.h: aclgan_ctx_set_augment);
-        z_ms (tests): this update's (z_4, z_5) instead of a draw (ms_lambda; include/aclgan_hip.h: aclgan_ctx_set_modeseek)"""
-        self._update("gen", x_a, x_b, hyperparameters, z, aug, z_ms)
+        z_ms (tests): this update's (z_4, z_5) instead of a draw (ms_lambda; include/aclgan_hip.h: aclgan_ctx_set_modeseek);
+        aug_u (tests): this update's (5 B, 4) gate uniforms instead of a draw (dis_augment_p; include/aclgan_hip.h: aclgan_augment_gate)"""
+        self._update("gen", x_a, x_b, hyperparameters, z, aug, z_ms, aug_u)
 
     def modeseek_log_text(self):
         """train.py's log-line suffix: the two mode-seeking values of the last gen_update and the two collapse readouts"""
         return " ms_A=%.4g ms_B=%.4g div_A=%.4g div_B=%.4g" % (float(self.loss_gen_ms_A), float(self.loss_gen_ms_B), float(self.gen_diversity_A),
                                                                float(self.gen_diversity_B))
 
-    def dis_update(self, x_a, x_b, hyperparameters, z=None, aug=None):
-        """aug (tests): this update's (7 B, 8) augmentation rows instead of a draw"""
-        self._update("dis", x_a, x_b, hyperparameters, z, aug)
+    def dis_update(self, x_a, x_b, hyperparameters, z=None, aug=None, aug_u=None):
+        """aug (tests): this update's (7 B, 8) augmentation rows instead of a draw; aug_u (tests): its (7 B, 4) gate uniforms instead of a draw"""
+        self._update("dis", x_a, x_b, hyperparameters, z, aug, aug_u=aug_u)
+
+    # ---- adaptive augmentation probability (dis_augment_p; not in the reference) ----
+    def ada_state(self):
+        """{'p', 'r_t', 'r', 'updates', 'adjustments'} of the device state in one device-to-host copy: the probability the next gate reads, the
+        mean overfitting signal of the last closed interval, the signal of the last dis_update, the dis_updates folded and the intervals closed
+        with a finite r_t (include/aclgan_hip.h: aclgan_ctx_set_ada)"""
+        if self._ada is None:
+            raise L.AclganError("ada_state(): the adaptive augmentation probability is off (set dis_augment_p)")
+        t = self._ada.cpu()
+        n = t.view(torch.int32)
+        return {"p": float(t[0]), "r_t": float(t[1]), "r": float(t[6]), "updates": int(n[4]), "adjustments": int(n[5])}
+
+    def ada_log_text(self):
+        """train.py's log-line suffix: p and the last closed interval's r_t"""
+        s = self.ada_state()
+        return " ada_p=%.4g ada_rt=%.4g" % (s["p"], s["r_t"])
 
     def update_learning_rate(self):   # trainer.py:295-299, called every iteration (train.py:101)
         self._sched_calls += 1
@@ -1252,6 +1366,11 @@ class aclgan_Trainer:
             # the LeCam state as the device holds it (anchors, the count's four bytes).  The name holds neither "gen" nor "dis" either
             # (decay: resume() warns when the resuming run's differs)
             torch.save({"state": self._lecam.cpu().clone(), "decay": self.lecam_decay}, os.path.join(snapshot_dir, "lecam_%08d.pt" % (iterations + 1)))
+        if self._ada is not None:
+            # the state as the device holds it (p, the open interval, the counters' four bytes) and the controller's three parameters.  The
+            # name holds neither "gen" nor "dis" either
+            torch.save({"state": self._ada.cpu().clone(), "target": self.ada[2], "interval": self.ada[3], "kimg": self.ada[4]},
+                       os.path.join(snapshot_dir, "ada_%08d.pt" % (iterations + 1)))
 
     @staticmethod
     def _get_model_list(dirname, key):   # utils.py:211-220
@@ -1319,6 +1438,24 @@ class aclgan_Trainer:
                 import warnings
                 warnings.warn("aclgan_Trainer.resume: %s not found; the LeCam anchors start again (the term acts after lecam_start more updates)" % lecam_name)
                 self._lecam.zero_()
+        if self._ada is not None:
+            import warnings
+            ada_name = os.path.join(checkpoint_dir, "ada_%08d.pt" % iterations)
+            if os.path.isfile(ada_name):
+                sd = torch.load(ada_name, map_location="cpu")
+                if tuple(sd["state"].shape) != tuple(self._ada.shape):
+                    raise L.AclganError("resume: %s holds %d floats, the state has %d" % (ada_name, sd["state"].numel(), self._ada.numel()))
+                self._ada.copy_(sd["state"].to(self.device, torch.float32))
+                if not self.ada[1]:      # a fixed probability is the configured one, whatever the file says; the monitor's counters continue
+                    self._ada[0] = self.ada[0]
+                saved = (sd.get("target"), sd.get("interval"), sd.get("kimg"))
+                if saved != tuple(self.ada[2:]):
+                    warnings.warn("aclgan_Trainer.resume: %s was written with (ada_target, ada_interval, ada_kimg) = %r, this run uses %r; the saved "
+                                  "p and interval continue under the new parameters" % (ada_name, saved, tuple(self.ada[2:])))
+            else:
+                warnings.warn("aclgan_Trainer.resume: %s not found; the augmentation probability starts again at %g" % (ada_name, self.ada[0]))
+                self._ada.zero_()
+                self._ada[0] = self.ada[0]
         self._hp = hyperparameters
         self._setup_data_parallel()
         print("Resume from iteration %d" % iterations)

@@ -309,6 +309,42 @@ int aclgan_ctx_set_augment(aclgan_ctx* ctx, int policy, const float* params, int
  * and needs no GPU (0 for a null context); aclgan_step_algorithmic_bytes counts the fold while a state is bound. */
 size_t aclgan_lecam_state_floats(aclgan_ctx* ctx);
 int aclgan_ctx_set_lecam(aclgan_ctx* ctx, float lambda, float decay, int start, float* state);
+/* Adaptive strength of the discriminator augmentation (NOT in the reference; Karras et al., NeurIPS 2020, "Training Generative Adversarial
+ * Networks with Limited Data", ADA).  One probability p lives in a device state; a gate applies it to the augmentation
+ * rows, a sign statistic of the discriminators' outputs on real images measures overfitting, a controller moves p.  No host synchronisation.
+ * state: DEVICE memory of aclgan_ada_state_floats() = 12 floats, zero-initialised by the caller except p:
+ *     [0] p, the probability the gate reads          [1] r_t, the mean r of the last closed interval
+ *     [2] interval sum of r                          [3] interval count (as a float)
+ *     [4] updates folded (int32 in the float's bytes) [5] adjustments made: intervals closed with a finite r_t (int32)
+ *     [6] r of the last update (NaN where it was not finite)   [7] 0
+ *     [8], [9]   this update's (sum of w q, sum of w) of dis_A's passes        [10], [11]   the same of dis_B's
+ * Slots 8 .. 11 extend the eight published slots: dis_A and dis_B run on different streams of an update, so each adds onto a pair of its own.
+ * With a state bound, aclgan_dis_update changes in two places and nowhere else (aclgan_gen_update not at all; the 16 losses keep their values):
+ *   sign   behind the loss launch of every train pass of dis_A / dis_B that has a term of target 1 (the real side: x_a, x_b), ONE launch of
+ *          ada_sign_kernel: per such term (map o of n elements, reported weight w) q = mean(sgn(o - 0.5)), sgn(0) = 0, a NaN in o makes q NaN;
+ *          pair += (w q, w), terms in index order, no atomics.  0.5 is the LSGAN decision boundary between the targets 0 and 1, the counterpart
+ *          of ADA's sign of the logit.  dis_2 contributes nothing: both of its inputs are generated.
+ *   fold   after the lanes have joined (behind the LeCam fold), one launch of ada_fold_kernel:
+ *              r = (pair_A[0] + pair_B[0]) / (pair_A[1] + pair_B[1]);   [6] = r;   the pairs are zeroed
+ *              a finite r:  [2] += r, [3] += 1          a non-finite r leaves p, r_t and the interval sum as they are
+ *              [4] += 1;   when [4] % interval == 0:
+ *                  if [3] > 0:  r_t = [2] / [3];  p = clamp(p + sgn(r_t - target) * step, 0, 1) as one fp32 add;  [5] += 1
+ *                  [2] = [3] = 0
+ *          step == 0 never moves p (a fixed probability) and still publishes r and r_t.
+ * aclgan_ctx_set_ada keeps the pointer, not the contents (read and written stream-ordered, also under a captured graph); state == NULL switches
+ * the feature off (a context's default: the launches, buffers and bits of a context that never heard of it).  ACLGAN_EINVAL, with nothing
+ * enqueued, for a target outside [-1, 1] (NaN included), interval < 1, or a negative or non-finite step.  aclgan_ada_state_floats launches
+ * nothing and needs no GPU; aclgan_step_algorithmic_bytes counts the sign launches and the fold while a state is bound.
+ *
+ * aclgan_augment_gate is the gate, one launch, on caller-supplied DEVICE tensors: rows (n, 8) as aclgan_ctx_set_augment takes them, u (n, 4)
+ * uniforms in [0, 1) (column 3 unused), p = state[0] read on the device, rows_eff (n, 8) the output -- what aclgan_ctx_set_augment is then
+ * given.  For row r and operation k of policy (k = 0 color: columns 0..2, 1 translation: 3..4, 2 cutout: 5..6): u[r][k] < p (compared in
+ * fp32) copies the operation's columns, otherwise they become its neutral values 0, 1, 1 / 0, 0 / cx = W, cy = H.  Operations outside the
+ * policy and column 7 are copied.  A pure select: the output holds input bits.  ACLGAN_EINVAL, with nothing enqueued, for a null or
+ * aliasing buffer, n < 1, H or W < 1, or a policy outside 1 .. 7. */
+size_t aclgan_ada_state_floats(void);
+int aclgan_ctx_set_ada(aclgan_ctx* ctx, float* state, float target, int interval, float step);
+int aclgan_augment_gate(const float* rows, const float* u, const float* state, int n, int H, int W, int policy, float* rows_eff, void* stream);
 /* Mode-seeking regulariser of the generators (NOT in the reference; Mao et al., CVPR 2019, "Mode Seeking GANs for Diverse Image Synthesis";
  * DESIGN.md section 4g).  Only aclgan_gen_update changes.  With lambda > 0 it reads two more noise tensors z_4, z_5 of shape (B, style_dim) and
  * runs two more decoder passes on the content codes it already has:
@@ -732,6 +768,13 @@ int aclgan_lsgan_lecam_multi(const float* const* o, const int* n, const float* t
                              int nterms, float lambda, int start, const int* count, const float* lscale, void* stream);
 /* The fold of aclgan_ctx_set_lecam on a caller-supplied state of 18 num_scales + 4 floats (the layout above): one single-workgroup launch. */
 int aclgan_lecam_fold(float* state, int num_scales, float decay, void* stream);
+/* The sign statistic of aclgan_ctx_set_ada on caller-supplied maps (what a train pass of dis_A / dis_B runs while a state is bound): per term
+ * acc[0] += weight[i] * mean(sgn(o[i] - 0.5)), acc[1] += weight[i]; acc: device float[2].  The signs are counted as integers, so the mean is
+ * (count of o > 0.5 minus count of o < 0.5) / n rounded once; a NaN in a map makes its mean NaN.  One workgroup processes the terms in index
+ * order; more than 12 terms run as several launches.  ACLGAN_EINVAL for a null array or entry, n[i] < 1, a negative or non-finite weight. */
+int aclgan_ada_sign_multi(const float* const* o, const int* n, const float* weight, int nterms, float* acc, void* stream);
+/* The fold of aclgan_ctx_set_ada on a caller-supplied state of 12 floats (the layout above): one single-workgroup launch. */
+int aclgan_ada_fold(float* state, float target, int interval, float step, void* stream);
 /* recon_criterion (trainer.py:61-62): *loss_slot += mean|a[..., :3] - b| over npix pixels; a has a_channels (3 or 4) NHWC
  * channels, b has 3; d_a (may be NULL) (+)= gscale*sign/(3*npix) on channels 0-2 */
 int aclgan_l1_loss(const float* a, int a_channels, const float* b, int64_t npix, float* loss_slot, float* d_a, float gscale,

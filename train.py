@@ -172,7 +172,9 @@ def main():
                   # (grad_clip* on: the gradient norms of the last generator / discriminator update and the updates skipped for a non-finite norm)
                   (trainer.grad_clip_log_text() if max(trainer.grad_clip) > 0 else "") +
                   # (ms_lambda > 0: the mode-seeking values of the last gen_update and div = mean(dI / dz), which tends to 0 when z is ignored)
-                  (trainer.modeseek_log_text() if trainer.ms_lambda > 0 else ""))
+                  (trainer.modeseek_log_text() if trainer.ms_lambda > 0 else "") +
+                  # (dis_augment_p on: the augmentation probability the next update's gate reads and the overfitting signal of the last closed interval)
+                  (trainer.ada_log_text() if trainer.ada is not None else ""))
             loss_log.append(iterations + 1, vals.tolist())
         if display is not None and image_due(iterations, config, "image_save_iter"):      # train.py:83-90
             train_a, train_b, test_a, test_b = display
