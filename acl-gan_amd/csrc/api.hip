@@ -424,7 +424,7 @@ int aclgan_ada_fold(float* state, float target, int interval, float step, void* 
 int aclgan_lecam_fold(float* state, int num_scales, float decay, void* stream) {
     ACL_REQUIRE(state && num_scales >= 1, "lecam_fold: bad arguments");
     ACL_REQUIRE(decay >= 0.f && decay < 1.f, "lecam_fold: decay = %g lies outside [0, 1)", (double)decay);
-    return lecam_fold(state, num_scales, decay, (hipStream_t)stream);
+    return lecam_fold(state, num_scales, decay, false, (hipStream_t)stream);
 }
 int aclgan_l1_loss(const float* a, int a_channels, const float* b, int64_t npix, float* loss_slot, float* d_a, float gscale, int d_accumulate,
                    void* stream) {

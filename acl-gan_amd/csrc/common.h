@@ -250,6 +250,8 @@ int adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int6
 int nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, hipStream_t st);
 int nhwc_to_nchw(const float* src, float* dst, int B, int C, int H, int W, hipStream_t st);
 int fill_zero(float* p, int64_t n, hipStream_t st);
+// `bytes` zero bytes at p, stream-ordered: hipMemsetAsync, or a kernel where `st` is being captured (misc.hip: memset nodes went wrong on replay)
+int zero_async(void* p, size_t bytes, hipStream_t st);
 
 // small dense layers (MLP, style head): y[b][o] = act(sum_i x[b][i] W[o][i] + bias[o])
 int linear_fwd(int B, int I, int O, const float* x, const float* w, const float* bias, int act, float* y, hipStream_t st);
@@ -298,8 +300,8 @@ struct LecamTerm { LsganTerm ls; const float* anchor; float* lecam; float* stats
 int lsgan_lecam_batch(const LecamTerm* terms, int nterms, float lambda, int start, const int* count, hipStream_t st, const float* lscale = nullptr);
 // state layout of aclgan_ctx_set_lecam (S = num_scales): anchors [3][S][2] | sums [3][S][2][2] | lecam slots [3] | count (int32)
 static inline size_t lecam_state_floats(int S) { return (size_t)18 * S + 4; }
-// anchors <- the update's weighted means (copy at count 0, else decay*a + (1-decay)*m; a non-finite m is skipped), sums <- 0, count += 1
-int lecam_fold(float* state, int num_scales, float decay, hipStream_t st);
+// anchors <- the update's weighted means (copy at count 0, else decay*a + (1-decay)*m; a non-finite m is skipped -- whole: and with it every other anchor), sums <- 0, count += 1
+int lecam_fold(float* state, int num_scales, float decay, bool whole, hipStream_t st);
 // adaptive augmentation probability (ada.hip; include/aclgan_hip.h: aclgan_ctx_set_ada).  augment_gate: rows_eff[r] = rows[r] where
 // u[r][k] < state[0] for operation k of the policy, else the operation's neutral columns.  ada_sign: acc[0] += w mean(sgn(o - 0.5)), acc[1] += w
 // per term, in index order.  ada_fold: the update's r into the interval, p moved every `interval` updates, the per-update pairs zeroed.

@@ -729,8 +729,8 @@ static int launch_wgrad(const ConvGeom& g, WgP p, hipStream_t st, void* det_part
     float* dw_out = p.dw;
     const int64_t ndw = (int64_t)g.Co * p.Kn;
     if (det_part != nullptr && splits > 1) {      // deterministic mode: one zeroed copy of dw per pixel slice, added in order below
-        hipError_t e = hipMemsetAsync(det_part, 0, (size_t)splits * ndw * sizeof(float), st);
-        if (e != hipSuccess) return hip_fail(e, "memset wgrad slices");
+        const int zrc = zero_async(det_part, (size_t)splits * ndw * sizeof(float), st);
+        if (zrc) return zrc;
         p.dw = (float*)det_part; p.zs = ndw;
     }
     dim3 grid(p.nwg, 1, splits), block(WM * WN * 64);

@@ -245,8 +245,8 @@ int launch_fwd_fast(const ConvGeom& g, FwdFP p, hipStream_t st) {
         hipLaunchKernelGGL(ring_zero_kernel, dim3(cdiv(rows * (g.Co / 4), 256)), dim3(256), 0, st, p, rows);
         ACL_CHECK_LAUNCH("ring_zero_kernel");
     } else if (splits > 1) {
-        hipError_t e = hipMemsetAsync(p.y, 0, (size_t)g.M * g.Co * sizeof(float), st);
-        if (e != hipSuccess) return hip_fail(e, "memset y");
+        const int zrc = zero_async(p.y, (size_t)g.M * g.Co * sizeof(float), st);
+        if (zrc) return zrc;
     }
     hipLaunchKernelGGL((conv_fwd_fast_kernel<WM, WN, TM, TN>), dim3(p.nwg, 1, splits), dim3(WM * WN * 64), 0, st, p);
     ACL_CHECK_LAUNCH("conv_fwd_fast_kernel");
@@ -457,12 +457,12 @@ int launch_dgrad_fast(const ConvGeom& g, DgFP p, hipStream_t st) {
     if (nblk < 128 && nk_plan >= 32 && !sw(SW_DETERMINISTIC) && !p.ringpad)       // (the slices combine with fp32 atomics; ringpad: one plain store per position)
         p.ksplit = max(1, min(nk_plan / 8, 512 / nblk));   // floor: stay within one round of 512 resident workgroups
     if (p.ksplit > 1 && p.mode == 0) {
-        hipError_t e = hipMemsetAsync(p.dxp, 0, conv_dgrad_scratch_bytes(g), st);
-        if (e != hipSuccess) return hip_fail(e, "memset dxp");
+        const int zrc = zero_async(p.dxp, conv_dgrad_scratch_bytes(g), st);
+        if (zrc) return zrc;
     }
     if (p.ksplit > 1 && p.mode == 1 && !p.accumulate) {
-        hipError_t e = hipMemsetAsync(p.dxp, 0, (size_t)g.B * g.Hi * g.Wi * g.Ci * sizeof(float), st);
-        if (e != hipSuccess) return hip_fail(e, "memset dx");
+        const int zrc = zero_async(p.dxp, (size_t)g.B * g.Hi * g.Wi * g.Ci * sizeof(float), st);
+        if (zrc) return zrc;
     }
     hipLaunchKernelGGL((conv_dgrad_fast_kernel<WM, WN, TM, TN>), dim3(p.nwg, 1, g.s * g.s * p.ksplit), dim3(WM * WN * 64), 0, st, p);
     ACL_CHECK_LAUNCH("conv_dgrad_fast_kernel");
@@ -503,8 +503,8 @@ int dgrad_fast_all(const ConvGeom& g, DgFP p, float* dxp, float* dx, int accumul
         if (g.p > 0 && sw(SW_DETERMINISTIC)) {
             // ordered reflection backward: the ring positions are STORED on a zeroed padded grid (one writer each; the scratch is
             // free again -- the Winograd planes of the interior are consumed) and conv_fold adds them onto their targets
-            hipError_t e = hipMemsetAsync(dxp, 0, (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float), st);
-            if (e != hipSuccess) return hip_fail(e, "memset padded grid");
+            const int zrc = zero_async(dxp, (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float), st);
+            if (zrc) return zrc;
             p.mode = 2; p.ringpad = 1; p.dxp = dxp; p.accumulate = 0;
             rc = launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
             if (rc) return rc;
@@ -874,8 +874,8 @@ int launch_wgrad_fast(const ConvGeom& g, WgFP p, hipStream_t st, void* det_part 
     float* dw_out = p.dw; float* db_out = p.db;
     const int64_t ndw = (int64_t)ny * g.Co * p.Kn;
     if (det_part != nullptr && splits > 1) {
-        hipError_t e = hipMemsetAsync(det_part, 0, (size_t)splits * (ndw + g.Co) * sizeof(float), st);
-        if (e != hipSuccess) return hip_fail(e, "memset wgrad slices");
+        const int zrc = zero_async(det_part, (size_t)splits * (ndw + g.Co) * sizeof(float), st);
+        if (zrc) return zrc;
         p.dw = (float*)det_part; p.dw_zs = ndw;
         if (p.db) { p.db = (float*)det_part + (size_t)splits * ndw; p.db_zs = g.Co; }
     }
@@ -943,8 +943,8 @@ template <int WM, int WN, int TM, int TN>
 int up5_wgrad_t(const ConvGeom& g, const float* x, const float* dy, float* dw, float* db, float* dwp, hipStream_t st, const float* haveV) {
     // (1) phase weight gradients: valid 3x3 wgrad on the low-res input against the strided views of dy
     const size_t nb = (size_t)4 * g.Co * 9 * g.Ci * sizeof(float);
-    hipError_t e = hipMemsetAsync(dwp, 0, nb, st);
-    if (e != hipSuccess) return hip_fail(e, "memset dwp");
+    const int zrc = zero_async(dwp, nb, st);
+    if (zrc) return zrc;
     const bool kc = wgrad_kc_ok(g);
     void* part = (char*)dwp + up5_dwp_bytes(g);      // partial tiles of the ordered-slice kernels follow the phase gradients
     WgFP p;
@@ -1007,8 +1007,8 @@ int up5_dgrad_t(const ConvGeom& g, const float* dy, const float* w, float* dx, i
     p.dyv = 0; p.band = 6; p.upshift = 1; p.Hd = g.Hi; p.Wd = g.Wi;
     if (sw(SW_DETERMINISTIC)) {     // band positions stored on a zeroed padded hi-res grid (after the merged filters), then the fold gather
         float* dxp = (float*)((char*)wp + up5_merged_bytes(g));
-        hipError_t e = hipMemsetAsync(dxp, 0, (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float), st);
-        if (e != hipSuccess) return hip_fail(e, "memset padded grid");
+        const int zrc = zero_async(dxp, (size_t)g.B * g.Hp * g.Wp * g.Ci * sizeof(float), st);
+        if (zrc) return zrc;
         p.ringpad = 1; p.dxp = dxp; p.accumulate = 0;
         const int rc = launch_dgrad_fast<WM, WN, TM, TN>(g, p, st);
         if (rc) return rc;

@@ -450,8 +450,8 @@ int launch_dgrad16(const ConvGeom& g, DgFP p, hipStream_t st) {
     const int nk_plan = (p.mode == 2 && p.band == 0) ? std::max(g.Co / (16 * KS), nk_min / ((g.k + g.s - 1) / g.s)) : nk_min;   // halo: useful taps only
     if (nblk < 128 && nk_plan * KS >= 32 && !sw(SW_DETERMINISTIC)) p.ksplit = max(1, min(nk_plan * KS / 8, 512 / nblk));   // (slices combine with atomics)
     if (p.ksplit > 1 && p.mode == 1 && !p.accumulate) {
-        hipError_t e = hipMemsetAsync(p.dxp, 0, (size_t)g.B * g.Hi * g.Wi * g.Ci * sizeof(float), st);
-        if (e != hipSuccess) return hip_fail(e, "memset dx");
+        const int zrc = zero_async(p.dxp, (size_t)g.B * g.Hi * g.Wi * g.Ci * sizeof(float), st);
+        if (zrc) return zrc;
     }
     hipLaunchKernelGGL((conv_dgrad16_kernel<T, KS, WM, WN, TM, TN>), dim3(p.nwg, 1, g.s * g.s * p.ksplit), dim3(WM * WN * 64), 0, st, p);
     ACL_CHECK_LAUNCH("conv_dgrad16_kernel");
@@ -881,8 +881,8 @@ int wgrad16_t(const ConvGeom& g, const float* x, const float* dy, float* dw, flo
     if (up5_eligible(g)) {
         float* dwp = (float*)scratch;
         void* part = (char*)scratch + up5_dwp_bytes(g);
-        hipError_t e = hipMemsetAsync(dwp, 0, (size_t)4 * g.Co * 9 * g.Ci * sizeof(float), st);
-        if (e != hipSuccess) return hip_fail(e, "memset dwp");
+        const int zrc = zero_async(dwp, (size_t)4 * g.Co * 9 * g.Ci * sizeof(float), st);
+        if (zrc) return zrc;
         WgFP p = wg_params(g, x, dy, dwp, db, xst, dyst);
         p.Ho = g.Hi - 2; p.Wo = g.Wi - 2; p.k = 3; p.s = 1; p.p = 0; p.up = 0; p.Hu = g.Hi; p.Wu = g.Wi;
         p.P = g.B * p.Ho * p.Wo; p.Kn = 9 * g.Ci; p.phases = 1; p.Hf = g.Ho; p.Wf = g.Wo;

@@ -119,8 +119,7 @@ static int gen_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     float* sums = c.allocf((int64_t)3 * nfs);
     NEED(sums);
     if (!c.dry) {
-        hipError_t e = hipMemsetAsync(L, 0, sizeof(float) * (ACLGAN_L_GEN_TOTAL + 1), c.st);
-        if (e != hipSuccess) return hip_fail(e, "memset losses");
+        CHK(zero_async(L, sizeof(float) * (ACLGAN_L_GEN_TOTAL + 1), c.st));
     }
     StepIn in;
     auto& [xa, xb, z1, z2, z3, c1, c2] = in;
@@ -254,12 +253,9 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
                 focus ? ">" : "<=", focus ? 4 : 3, c.arch.gen_output_dim);
     const int AB = ACLGAN_NET_GEN_AB, BA = ACLGAN_NET_GEN_BA;
     if (!c.dry) {
-        hipError_t e = hipMemsetAsync(L + ACLGAN_L_DIS_A, 0, sizeof(float) * 4, c.st);
-        if (e != hipSuccess) return hip_fail(e, "memset losses");
-        if (c.lecam_state) {      // this update's three lecam slots start at zero, like its losses
-            e = hipMemsetAsync(c.lecam_state + 18 * c.arch.dis_num_scales, 0, sizeof(float) * 3, c.st);
-            if (e != hipSuccess) return hip_fail(e, "memset lecam slots");
-        }
+        CHK(zero_async(L + ACLGAN_L_DIS_A, sizeof(float) * 4, c.st));
+        if (c.lecam_state)      // this update's three lecam slots start at zero, like its losses
+            CHK(zero_async(c.lecam_state + 18 * c.arch.dis_num_scales, sizeof(float) * 3, c.st));
     }
     StepIn in;
     auto& [xa, xb, z1, z2, z3, c1, c2] = in;
@@ -319,7 +315,7 @@ static int dis_update_impl(aclgan_ctx& c, const float* x_a, const float* x_b, co
     }
     if (c.lecam_state) {      // every launch that read anchors lies before the join: the anchors move for the NEXT update
         c.count(2.0 * 4.0 * (double)lecam_state_floats(c.arch.dis_num_scales));
-        RUN(lecam_fold(c.lecam_state, c.arch.dis_num_scales, c.lecam_decay, c.st));
+        RUN(lecam_fold(c.lecam_state, c.arch.dis_num_scales, c.lecam_decay, true, c.st));
     }
     if (c.ada_state) {        // every sign launch lies before the join: r of this update into the interval, p moves for the NEXT update's gate
         c.count(2.0 * 4.0 * (double)ada_state_floats());

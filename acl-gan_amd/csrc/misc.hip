@@ -138,12 +138,25 @@ int cast_storage(const void* src, int src_st, void* dst, int dst_st, int64_t n, 
 __global__ void fill_zero_kernel(float* p, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 0.f;
 }
-int fill_zero(float* p, int64_t n, hipStream_t st) {
-    if (n == 0) return ACLGAN_OK;
-    hipError_t e = hipMemsetAsync(p, 0, (size_t)n * sizeof(float), st);
+// Zero-fill on a stream.  Eagerly hipMemsetAsync.  On a stream that is being captured into a graph a kernel of ours instead: a captured
+// hipMemsetAsync becomes a memset node, and from its second replay on the runtime's memset node filled the buffer with an 8-byte pattern that
+// was not zero (seen: the first node of a captured dis_update, the whole gradient buffer; tests/test_gpu_graph.py compares the flat buffers).
+// A kernel node carries its arguments by value.
+int zero_async(void* p, size_t bytes, hipStream_t st) {
+    if (bytes == 0) return ACLGAN_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone && bytes % sizeof(float) == 0 && (uintptr_t)p % sizeof(float) == 0) {
+        const int64_t n = (int64_t)(bytes / sizeof(float));
+        hipLaunchKernelGGL(fill_zero_kernel, dim3((int)std::min<int64_t>(cdiv64(n, 256), 4096)), dim3(256), 0, st, (float*)p, n);
+        ACL_CHECK_LAUNCH("fill_zero_kernel");
+        return ACLGAN_OK;
+    }
+    hipError_t e = hipMemsetAsync(p, 0, bytes, st);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
     return ACLGAN_OK;
 }
+int fill_zero(float* p, int64_t n, hipStream_t st) { return zero_async(p, (size_t)n * sizeof(float), st); }
 
 // ---- AvgPool2d(3, stride 2, pad 1, count_include_pad=False) ----
 __global__ void avgpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C, int Ho, int Wo) {
@@ -940,23 +953,28 @@ int lsgan_lecam_batch(const LecamTerm* terms, int nterms, float lambda, int star
     return ACLGAN_OK;
 }
 // the fold: 6 S anchors, one thread each; every thread has read count before thread 0 advances it
-__global__ void __launch_bounds__(64) lecam_fold_kernel(float* __restrict__ state, int S, float decay) {
+// whole: an update's fold.  One non-finite mean means the update itself is non-finite (its loss holds that map) and will be skipped by the
+// gradient-norm guard or the loss scale: then NO anchor moves, so that a skipped update leaves the anchors as it found them.
+__global__ void __launch_bounds__(64) lecam_fold_kernel(float* __restrict__ state, int S, float decay, int whole) {
     float* anchors = state;
     float* sums = state + 6 * S;
     int* count = reinterpret_cast<int*>(state + 18 * S + 3);
     const int cnt = count[0];
-    __syncthreads();
+    int bad = 0;
+    if (whole)
+        for (int i = threadIdx.x; i < 6 * S; i += 64) bad |= sums[2 * i + 1] > 0.f && !isfinite(sums[2 * i] / sums[2 * i + 1]);
+    bad = __syncthreads_or(bad);
     for (int i = threadIdx.x; i < 6 * S; i += 64) {
         const float sm = sums[2 * i], sw = sums[2 * i + 1];
         const float m = sm / sw;      // (a class without a term: 0 / 0, skipped below)
-        if (sw > 0.f && isfinite(m)) anchors[i] = cnt == 0 ? m : decay * anchors[i] + (1.f - decay) * m;
+        if (sw > 0.f && isfinite(m) && !bad) anchors[i] = cnt == 0 ? m : decay * anchors[i] + (1.f - decay) * m;
         sums[2 * i] = 0.f; sums[2 * i + 1] = 0.f;
     }
     if (threadIdx.x == 0) count[0] = cnt + 1;
 }
-int lecam_fold(float* state, int num_scales, float decay, hipStream_t st) {
+int lecam_fold(float* state, int num_scales, float decay, bool whole, hipStream_t st) {
     ACL_REQUIRE(state && num_scales >= 1, "lecam_fold: bad arguments");
-    hipLaunchKernelGGL(lecam_fold_kernel, dim3(1), dim3(64), 0, st, state, num_scales, decay);
+    hipLaunchKernelGGL(lecam_fold_kernel, dim3(1), dim3(64), 0, st, state, num_scales, decay, whole ? 1 : 0);
     ACL_CHECK_LAUNCH("lecam_fold_kernel");
     return ACLGAN_OK;
 }

@@ -293,7 +293,10 @@ int aclgan_ctx_set_augment(aclgan_ctx* ctx, int policy, const float* params, int
  * S the live fp16 loss scale or 1; the anchors are constants of the gradient; aclgan_gen_update does not change.  After the lanes have
  * joined one more launch folds the update's statistics:
  *     m[D][s][k] = sum_{terms of class k} w * mean(o) / sum_{terms of class k} w
- *     a[D][s][k] = m if count == 0, else decay * a + (1 - decay) * m;   a non-finite m leaves a as it is
+ *     a[D][s][k] = m if count == 0, else decay * a + (1 - decay) * m;   one non-finite m leaves EVERY a as it is (the update that produced
+ *                  it has non-finite gradients too and gets skipped by the gradient-norm guard or the loss scale).  The guard looks at the
+ *                  means only: an update skipped for another reason -- an fp16 gradient overflow or an infinite norm behind finite
+ *                  discriminator outputs -- still folds its means and advances count
  *     count += 1;  the per-update sums are zeroed for the next update
  * Every launch that reads anchors precedes the fold: an update sees the anchors the previous update left.  With lam_eff == 0 the loss
  * slots and d_o hold exactly the bits of an update without a state.  The 16 losses keep their meaning and values.
@@ -766,7 +769,8 @@ int aclgan_lsgan_loss_multi(const float* const* o, const int* n, const float* ta
 int aclgan_lsgan_lecam_multi(const float* const* o, const int* n, const float* target, const float* weight, float* const* loss_slot,
                              float* const* d_o, const float* gscale, const float* const* anchor, float* const* lecam_slot, float* const* stats,
                              int nterms, float lambda, int start, const int* count, const float* lscale, void* stream);
-/* The fold of aclgan_ctx_set_lecam on a caller-supplied state of 18 num_scales + 4 floats (the layout above): one single-workgroup launch. */
+/* The fold of aclgan_ctx_set_lecam on a caller-supplied state of 18 num_scales + 4 floats (the layout above): one single-workgroup launch.
+ * Here every cell stands alone: a non-finite m leaves a as it is, that anchor and no other. */
 int aclgan_lecam_fold(float* state, int num_scales, float decay, void* stream);
 /* The sign statistic of aclgan_ctx_set_ada on caller-supplied maps (what a train pass of dis_A / dis_B runs while a state is bound): per term
  * acc[0] += weight[i] * mean(sgn(o[i] - 0.5)), acc[1] += weight[i]; acc: device float[2].  The signs are counted as integers, so the mean is
