@@ -22,6 +22,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import _lib as L
 
@@ -274,7 +275,6 @@ def shard_base_seed(world_size=1):
     torch.manual_seed hold different random default seeds)"""
     seed = int(torch.initial_seed()) % (2 ** 62)
     if world_size > 1:
-        import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
             box = [seed]
             dist.broadcast_object_list(box, src=0)

@@ -11,10 +11,14 @@ The flat gradient buffer of one optimizer (120 MB gen / 99 MB dis in fp32) is re
 large buckets: xGMI is point-to-point (7 links x ~153 GB/s per GPU), large messages keep RCCL on
 its bandwidth-optimal algorithms, and the step is O(100 ms) so latency is irrelevant.
 """
+import ctypes
 import os
+import warnings
 
 import torch
 import torch.distributed as dist
+
+from . import _lib as L
 
 BUCKET_ELEMS = 16 * 1024 * 1024   # 64 MB fp32 per collective (post-backward path)
 # overlapped path: smaller buckets become ready earlier.  4 M floats = 16 MB: still far above the size where an
@@ -68,8 +72,6 @@ class BucketReducer:
     ctx: the aclgan_ctx handle; grad_of(group) -> that group's flat gradient tensor."""
 
     def __init__(self, ctx, grad_of, world_size: int, bucket_elems: int = OVERLAP_BUCKET_ELEMS):
-        from . import _lib as L
-        self._L = L
         self.ctx, self.grad_of, self.world = ctx, grad_of, world_size
         self.bucket_elems = int(bucket_elems)
         self.use_avg = dist.get_backend() == "nccl"   # RCCL has ReduceOp.AVG; gloo (CPU tests) sums, then scales
@@ -78,8 +80,7 @@ class BucketReducer:
         L.check(L.lib.aclgan_set_grad_buckets(ctx, self.bucket_elems, self._cb, None), "set_grad_buckets")
 
     def close(self):
-        import ctypes
-        self._L.lib.aclgan_set_grad_buckets(self.ctx, 0, ctypes.cast(None, self._L.BUCKET_FN), None)
+        L.lib.aclgan_set_grad_buckets(self.ctx, 0, ctypes.cast(None, L.BUCKET_FN), None)
 
     def begin(self, group: int):
         self.works, self.order, self.error, self.group = [], [], None, group
@@ -105,3 +106,85 @@ class BucketReducer:
             if not self.use_avg:
                 chunk.mul_(1.0 / self.world)
         self.works = []
+
+
+class DataParallel:
+    """The data-parallel side of aclgan_Trainer, a base class of it (not in the reference): one process per GPU, full replicas"""
+
+    def _dist_world(self):
+        if not (dist.is_available() and dist.is_initialized()):
+            return 0
+        if dist.get_world_size() == 1 and os.environ.get("ACLGAN_BENCH_FORCE_DIST") != "1":
+            return 0
+        return dist.get_world_size()
+
+    def _setup_data_parallel(self):
+        """Called at the end of __init__ and resume(): replicas must START identical, whatever each rank's RNG did -- broadcast rank 0's
+        state; then hook the engine's bucket callback so that each gradient bucket's all-reduce starts while the rest of the backward is
+        still running (BucketReducer).
+        z noise: every rank draws its own shard's z from a generator seeded with initial_seed() + rank."""
+        self._reducer = None
+        self._exposed_events, self._exposed_ms = [], 0.0
+        world = self._dist_world()
+        if not world:
+            return
+        # parameters and Adam state; the average; spectral norm's u / v (not parameters); the LeCam anchors and ADA's p and counters -- which
+        # every rank then keeps for itself: each sees its own shard, neither is all-reduced (the ranks may drift apart in p)
+        start = [buf for grp in (L.GROUP_GEN, L.GROUP_DIS) for buf in (self._param[grp], self._m[grp], self._v[grp])]
+        start += [self._ema, self._sn_state if self._tensors[L.GROUP_SN_STATE] else None, self._lecam, self._ada]
+        for buf in (b for b in start if b is not None):
+            broadcast_flat(buf)
+        steps = torch.tensor([self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls], dtype=torch.int64, device=self.device)
+        dist.broadcast(steps, 0)
+        self._opt[0]["steps"], self._opt[1]["steps"], self._sched_calls = (int(v) for v in steps.tolist())
+        self._zgen = torch.Generator().manual_seed(torch.initial_seed() + dist.get_rank())
+        if os.environ.get("ACLGAN_DDP_OVERLAP", "1") != "0":
+            self._reducer = BucketReducer(self._ctx, lambda g: self._grad[g], world)
+        if self.hip_graph:
+            # HIP-graph replay is single-GPU only: the bucket callbacks and the forward sync point are host code that starts
+            # collectives from inside the update, which a captured graph cannot replay -- say so instead of silently ignoring the option
+            warnings.warn("aclgan_Trainer: hip_graph=True is ignored in data-parallel runs (world size %d): updates run eagerly" % world)
+            self.hip_graph = False
+        # optional: the reference's global-batch semantics of the focus losses (config key ddp_global_focus / env
+        # ACLGAN_DDP_GLOBAL_FOCUS=1): the 6 mask sums are all-reduced at a forward sync point of gen_update
+        if self._hp.get("ddp_global_focus", False) or os.environ.get("ACLGAN_DDP_GLOBAL_FOCUS") == "1":
+            def on_sync(user, ptr, n):
+                try:
+                    off = int(ptr) - self._ws.data_ptr()
+                    t = self._ws[off: off + 4 * n].view(torch.float32)
+                    dist.all_reduce(t, op=dist.ReduceOp.SUM)      # stream-ordered: the compute stream waits for it, the host does not
+                except BaseException as e:   # noqa: BLE001  (must not unwind through the C frames)
+                    self._sync_error = e
+            self._sync_error = None
+            self._sync_cb = L.SYNC_FN(on_sync)
+            L.check(L.lib.aclgan_set_forward_sync(self._ctx, self._sync_cb, None, world), "set_forward_sync")
+
+    def _allreduce_grads(self, grp):
+        """Average the flat gradient buffer over ranks with RCCL before Adam.  With the bucket reducer the collectives
+        were started from inside the backward (overlap) and are only waited for here; ACLGAN_DDP_OVERLAP=0 selects the
+        plain post-backward bucketed all-reduce.  No-op when torch.distributed is not initialised."""
+        world = self._dist_world()
+        if not world:
+            return
+        # GPU-side exposure of the exchange: the compute stream does nothing between these two events except wait for the
+        # collectives, so their distance is the part of the all-reduce that was NOT hidden behind the backward
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        if self._reducer is not None:
+            self._reducer.finish(grp)
+        else:
+            allreduce_flat(self._grad[grp], world)
+        ev[1].record()
+        self._exposed_events.append(ev)
+        if len(self._exposed_events) > 4096:
+            self.allreduce_exposed_ms()
+
+    def allreduce_exposed_ms(self, reset=True):
+        """total milliseconds the compute stream spent waiting for gradient collectives since the last call (synchronises)"""
+        torch.cuda.synchronize(self.device)
+        self._exposed_ms += sum(a.elapsed_time(b) for a, b in self._exposed_events)
+        self._exposed_events = []
+        v = self._exposed_ms
+        if reset:
+            self._exposed_ms = 0.0
+        return v

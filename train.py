@@ -65,9 +65,9 @@ def main():
     torch.cuda.set_device(local_rank)
     # the lane scheduler's streams before the process group's (HIP binds streams to hardware queues in creation order: include/aclgan_hip.h)
     import aclgan_amd  # noqa: F401
-    from aclgan_amd import _lib as _L
+    from aclgan_amd import _lib as L
     if os.environ.get("ACLGAN_WARM_STREAMS", "1") not in ("", "0"):
-        _L.check(_L.lib.aclgan_warm_streams(0), "warm_streams")
+        L.check(L.lib.aclgan_warm_streams(0), "warm_streams")
     if world > 1:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -79,8 +79,6 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
     is_main = rank == 0
 
-    import aclgan_amd  # noqa: F401
-    from aclgan_amd import _lib as L
     from aclgan_amd.trainer import aclgan_Trainer
 
     config = get_config(opts.config)
@@ -155,26 +153,17 @@ def main():
             display = [(torch.rand(display_size, 3, H, W, generator=dgen) * 2 - 1).cuda() for _ in range(4)]
         else:
             display = [visual.display_stack(l.dataset, display_size) for l in (train_loader_a, train_loader_b, test_loader_a, test_loader_b)]
-    clock = {"t0": time.time()}
+    clock, last = {"t0": time.time()}, {"epoch": epoch0}
 
     def on_iteration(info):      # train.py:78-99: log / snapshot, between the updates and the learning-rate step
-        iterations = info["iterations"]
+        iterations, last["epoch"] = info["iterations"], info["epoch"]      # (the pass index: for the final snapshot)
         if is_main and log_due(iterations, config):
             vals = trainer._losses.cpu()          # one D2H copy, implies the sync of train.py:75
             # (wall time since the previous iteration ended: the updates AND the batch's decode / transform and the learning-rate step)
             print("Iteration: %08d/%08d  %.3fs/it  " % (iterations + 1, max_iter, time.time() - clock["t0"]) +
                   " ".join("%s=%.4g" % (n[5:], float(vals[i])) for i, n in enumerate(L.LOSS_NAMES)
                            if n in ("loss_gen_total", "loss_dis_total", "loss_idt_A", "loss_gen_adv_A")) +
-                  # (r1_gamma > 0: the penalties of the last R1 pass; not among the 16 reference losses, not in losses.csv)
-                  (" r1_A=%.4g r1_B=%.4g" % (float(trainer.loss_dis_r1_A), float(trainer.loss_dis_r1_B)) if trainer.r1_gamma > 0 else "") +
-                  # (lecam_lambda > 0: the regulariser's values of the last dis_update and the first scale's anchors, mean D on real / on fake)
-                  (trainer.lecam_log_text() if trainer.lecam_lambda > 0 else "") +
-                  # (grad_clip* on: the gradient norms of the last generator / discriminator update and the updates skipped for a non-finite norm)
-                  (trainer.grad_clip_log_text() if max(trainer.grad_clip) > 0 else "") +
-                  # (ms_lambda > 0: the mode-seeking values of the last gen_update and div = mean(dI / dz), which tends to 0 when z is ignored)
-                  (trainer.modeseek_log_text() if trainer.ms_lambda > 0 else "") +
-                  # (dis_augment_p on: the augmentation probability the next update's gate reads and the overfitting signal of the last closed interval)
-                  (trainer.ada_log_text() if trainer.ada is not None else ""))
+                  trainer.log_suffix())      # (the readouts of the training keys that are on: not among the 16 reference losses)
             loss_log.append(iterations + 1, vals.tolist())
         if display is not None and image_due(iterations, config, "image_save_iter"):      # train.py:83-90
             train_a, train_b, test_a, test_b = display
@@ -196,13 +185,6 @@ def main():
                 json.dump({"seed": seed, "epoch": info["epoch"] + (1 if info["it"] + 1 >= batches_per_pass else 0), "it": info["it"],
                            "iterations": iterations + 1}, f)
         clock["t0"] = time.time()
-
-    last = {"epoch": epoch0}
-    _on = on_iteration
-
-    def on_iteration(info):      # noqa: F811  (remember the pass index for the final snapshot)
-        last["epoch"] = info["epoch"]
-        _on(info)
 
     iterations = run_epochs(trainer, epoch, config, iterations=iterations, max_iter=max_iter, on_iteration=on_iteration, epoch0=epoch0)
     if is_main:
