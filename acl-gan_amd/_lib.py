@@ -214,6 +214,8 @@ SIGNATURES = {
     "aclgan_image_batch_transform": (ci, [vp, C.POINTER(ImageDesc), vp, ci, vp, vp, ci, ci, vp]),
     "aclgan_image_grid_scratch_bytes": (sz, []),
     "aclgan_image_grid_u8": (ci, [C.POINTER(GridSrc), ci, ci, ci, ci, vp, vp, vp]),
+    "aclgan_translate_finish_scratch_bytes": (sz, [ci]),
+    "aclgan_translate_finish_u8": (ci, [vp, i64, ci, vp, i64, ci, ci, ci, vp, vp, vp, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,0 +1,234 @@
+"""Translating a folder of test images in batches (the counterpart of the reference's test_batch.py; its loop is lines 105-194).
+
+finish_u8         decoder outputs + input images of a batch -> the byte pictures that get written, on the device (csrc/finish.hip through
+                  aclgan_translate_finish_u8: focus blend, one value range per picture per image, normalisation, rounding to bytes)
+translate_batch   one encode of the batch, one decode per style column, finish_u8; every byte of the batch in ONE device buffer
+translate_folder  the driver: file order, grouping by shape, style draws, output paths, one device->host copy per batch, Pillow encodes in a
+                  thread pool while the next batch is decoded and translated
+
+PyTorch does the plumbing only: allocations, views, the host copies.  What the reference computes per image at batch 1 -- and test.py with
+it -- is computed here per batch; with batch_size 1 the written files are byte-identical to test.py's load_image -> translate -> save_image.
+"""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import torch
+
+from . import _lib as L
+from .data import GpuBatchTransform, ImageFolder, default_loader, resized_size
+from .visual import _dense
+
+PICTURES = ("bar", "mask", "input")
+MAX_WORKERS = 16
+
+
+def finish_u8(dec, images=None, outputs=None, out=None, stream=None):
+    """dec (B, 4 or 3, H, W): decoder outputs (or a 3-channel slice of them), images (B, 3, H, W): what was translated -- device fp32
+    tensors; any batch stride passes without a copy (batch slices, channel slices), as in visual.image_grid.
+    outputs: which of 'bar', 'mask', 'input' to make (default: all that the arguments allow: 'mask' needs 4 channels, 'input' the images).
+    out: optional dict of preallocated contiguous (B, H, W, 3) uint8 device tensors to write into (views of one buffer: translate_batch).
+    Returns {name: uint8 (B, H, W, 3)} on dec's device; include/aclgan_hip.h states the rule.  Nothing is synchronised."""
+    dev = dec.device
+    if dev.type != "cuda":
+        raise L.AclganError("finish_u8: tensors must be on the GPU (got %s); there is no CPU path" % dev)
+    if dec.dim() != 4 or dec.shape[1] not in (3, 4) or dec.shape[0] < 1:
+        raise L.AclganError("finish_u8: expected a (B, 3 or 4, H, W) decoder output, got %s" % (tuple(dec.shape),))
+    B, Cd, H, W = dec.shape
+    if images is not None and (tuple(images.shape) != (B, 3, H, W) or images.device != dev):
+        raise L.AclganError("finish_u8: expected (%d, 3, %d, %d) images on %s, got %s on %s" % (B, H, W, dev, tuple(images.shape), images.device))
+    if outputs is None:
+        outputs = [n for n in PICTURES if (n != "mask" or Cd == 4) and (n != "input" or images is not None)]
+    outputs = list(outputs)
+    if not outputs or any(n not in PICTURES for n in outputs):
+        raise L.AclganError("finish_u8: outputs must be a non-empty subset of %s, got %s" % (PICTURES, outputs))
+    with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        d = _dense(dec)                  # (kept alive until the launches are enqueued; the caching allocator is stream-ordered)
+        g = _dense(images) if images is not None else None
+        res = {}
+        for n in outputs:
+            t = out[n] if out is not None else torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+            if tuple(t.shape) != (B, H, W, 3) or t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
+                raise L.AclganError("finish_u8: out[%r] must be a contiguous (%d, %d, %d, 3) uint8 tensor on %s" % (n, B, H, W, dev))
+            res[n] = t
+        scratch = torch.empty(L.lib.aclgan_translate_finish_scratch_bytes(B), dtype=torch.uint8, device=dev)
+        L.check(L.lib.aclgan_translate_finish_u8(L.ptr(d), d.stride(0) if B > 1 else 0, Cd, L.ptr(g), g.stride(0) if g is not None and B > 1 else 0,
+                                                 B, H, W, L.ptr(res.get("bar")), L.ptr(res.get("mask")), L.ptr(res.get("input")),
+                                                 L.ptr(scratch), L.stream_ptr(dev)), "translate_finish_u8")
+    return res
+
+
+def translate_batch(trainer, images, styles, a2b=True, with_input=True):
+    """reference test_batch.py:115,137-142 for a whole batch: ONE encode of images (B, 3, H, W), one decode per style column of styles
+    (B, S, style_dim, 1, 1) -- every image has its own style rows -- and the pictures of all of them through finish_u8.
+    Reads the weights trainer.ema_weights() selects, as encode / decode do.  Returns a dict:
+      dec     list of S raw decoder outputs (B, output_dim, H, W)
+      images  the batch on the device
+      bar     list of S uint8 (B, H, W, 3);  mask  the same when the configuration has a focus channel, else None
+      input   uint8 (B, H, W, 3), or None without with_input
+      bytes   the one uint8 device buffer (P, B, H, W, 3) all of those are views of, P = S (x 2 with masks) (+ 1 with the input)"""
+    gen = trainer.gen_AB if a2b else trainer.gen_BA
+    focus = trainer.focus_lam > 0
+    images = images.to(trainer.device, torch.float32)
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise L.AclganError("translate_batch: expected (B, 3, H, W) images, got %s" % (tuple(images.shape),))
+    B, _, H, W = images.shape
+    if styles.dim() != 5 or styles.shape[0] != B or styles.shape[1] < 1:
+        raise L.AclganError("translate_batch: expected (%d, S, style_dim, 1, 1) styles, got %s" % (B, tuple(styles.shape)))
+    S = styles.shape[1]
+    styles = styles.to(trainer.device, torch.float32)
+    with torch.no_grad():
+        content, _ = gen.encode(images)
+        per = 2 if focus else 1
+        buf = torch.empty(S * per + (1 if with_input else 0), B, H, W, 3, dtype=torch.uint8, device=trainer.device)
+        res = {"dec": [], "images": images, "bar": [], "mask": [] if focus else None, "input": buf[S * per] if with_input else None, "bytes": buf}
+        for j in range(S):
+            dec = gen.decode(content, styles[:, j])
+            out = {"bar": buf[j * per]}
+            if focus:
+                out["mask"] = buf[j * per + 1]
+            if with_input and j == 0:
+                out["input"] = res["input"]
+            finish_u8(dec if focus else dec[:, :3], images, outputs=list(out), out=out)      # (test.py: outputs[:, :3] without a focus loss)
+            res["dec"].append(dec)
+            res["bar"].append(out["bar"])
+            if focus:
+                res["mask"].append(out["mask"])
+    return res
+
+
+# ---- the folder driver ----
+def list_files(input_folder, max_images=3000):
+    """ImageFolder's files in its (sorted) order, the first max_images of them (the reference stops at 3000; 0: no cap)"""
+    try:
+        files = ImageFolder(input_folder).imgs
+    except (RuntimeError, AssertionError) as e:
+        raise L.AclganError("translate_folder: no images to translate in %s (%s)" % (input_folder, str(e).splitlines()[0]))
+    return files[:max_images] if max_images and max_images > 0 else files
+
+
+def image_size(path):
+    """(width, height) from the file's header, without decoding it"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.size
+
+
+def plan_batches(files, new_size, multiple, batch_size, size_of=image_size):
+    """Consecutive files of equal resized shape form a batch of at most batch_size; a change of shape closes the batch.  Raises before
+    anything runs for a file whose resized H or W is no multiple of `multiple` (2 ** gen.n_downsample: the decoder would return another size
+    than the encoder was given, and the blend with the input would fail).  Returns a list of batches, each a list of (index, path, (H, W))."""
+    if batch_size < 1:
+        raise L.AclganError("translate_folder: batch_size must be positive, got %d" % batch_size)
+    batches, cur = [], []
+    for i, path in enumerate(files):
+        w, h = size_of(path)
+        ow, oh = resized_size(w, h, new_size)
+        if oh % multiple or ow % multiple:
+            raise L.AclganError("translate_folder: %s is %dx%d (H x W) after Resize(%s); the generators take multiples of %d"
+                                % (path, oh, ow, new_size, multiple))
+        if cur and (cur[0][2] != (oh, ow) or len(cur) == batch_size):
+            batches.append(cur)
+            cur = []
+        cur.append((i, path, (oh, ow)))
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def draw_styles(n_images, num_style, style_dim, synchronized=False):
+    """The reference's draws in its order, from torch's CPU default generator (test_batch.py:105,117): style_fixed = randn(3 num_style, ...)
+    first, then -- unless synchronized -- one randn(3 num_style, ...) per image in folder order; every draw times 2, style j = row 3 j (the
+    rows 3 j + 1 and 3 j + 2 feed the cycle passes that are not run).  Returns (n_images, num_style, style_dim, 1, 1) on the host: the
+    values depend on the folder order only, never on how the images are grouped into batches."""
+    fixed = torch.randn(num_style * 3, style_dim, 1, 1)
+    rows = []
+    for _ in range(n_images):
+        s = fixed if synchronized else torch.randn(num_style * 3, style_dim, 1, 1)
+        rows.append((s * 2)[0::3])
+    return torch.stack(rows) if rows else torch.empty(0, num_style, style_dim, 1, 1)
+
+
+def output_paths(output_folder, path, index, num_style, focus, output_only=False):
+    """the files one input produces (test_batch.py:161-163,181,194): {'bar': [S paths], 'mask': [S paths] or None, 'input': path or None}"""
+    base = os.path.basename(path)
+    return {"bar": [os.path.join(output_folder, "_%02d_bar" % j, base) for j in range(num_style)],
+            "mask": [os.path.join(output_folder, "_%02d_mask" % j, base) for j in range(num_style)] if focus else None,
+            "input": None if output_only else os.path.join(output_folder, "input%03d.jpg" % index)}
+
+
+def _save(arr, path):
+    from PIL import Image
+    Image.fromarray(arr).save(path)          # the format follows the extension, as in torchvision's save_image
+
+
+def _to_host(t):
+    """one copy of a batch's bytes into pinned memory; the caller's stream has finished when it returns"""
+    if not t.is_cuda:
+        return t
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    torch.cuda.current_stream(t.device).synchronize()
+    return host
+
+
+def translate_folder(trainer, config, input_folder, output_folder, a2b=True, num_style=1, synchronized=False, output_only=False,
+                     batch_size=8, max_images=3000, keep_float=False, forward=None, transform=None):
+    """The reference's test_batch.py loop.  Per input file <out>/_%02d_bar/<basename> for every style, <out>/_%02d_mask/<basename> when
+    focus_loss > 0, <out>/input%03d.jpg unless output_only.  The passes whose saves the reference has commented out (_hat, _til) are not run.
+    forward(trainer, images, styles, a2b, with_input) / transform(list of decoded images): the device halves (translate_batch and
+    GpuBatchTransform(new_size, train=False, crop=False)); replaceable, so that the planning can be checked where there is no GPU.
+    Returns a list of (path, (H, W), batch index) records in folder order; with keep_float (for tests) a pair of that list and
+    {path: {'dec': [S tensors (C, H, W)], 'input': (3, H, W)}} on the host."""
+    gen_cfg = config["gen"]
+    focus = config["focus_loss"] > 0
+    if "new_size" in config:
+        new_size = config["new_size"]
+    else:
+        new_size = config["new_size_a"] if a2b else config["new_size_b"]
+    if num_style < 1:
+        raise L.AclganError("translate_folder: num_style must be positive, got %d" % num_style)
+    files = list_files(input_folder, max_images)
+    batches = plan_batches(files, new_size, 2 ** gen_cfg["n_downsample"], batch_size)
+    styles = draw_styles(len(files), num_style, gen_cfg["style_dim"], synchronized)
+    if forward is None:
+        forward = translate_batch
+    if transform is None:
+        transform = GpuBatchTransform(new_size, None, None, train=False, crop=False, device=trainer.device)
+    paths = [output_paths(output_folder, p, i, num_style, focus, output_only) for i, p in enumerate(files)]
+    for d in sorted({os.path.dirname(q) for o in paths for q in o["bar"] + (o["mask"] or []) + ([o["input"]] if o["input"] else [])}):
+        os.makedirs(d, exist_ok=True)
+
+    records, floats, pending = [], {}, []
+    pool = ThreadPoolExecutor(max_workers=min(MAX_WORKERS, max(4, 2 * batch_size)))
+    try:
+        decode = lambda b: [pool.submit(default_loader, p) for _, p, _ in batches[b]]
+        nxt = decode(0)
+        for b, batch in enumerate(batches):
+            cur = nxt
+            nxt = decode(b + 1) if b + 1 < len(batches) else None      # the decode of batch b+1 overlaps everything below
+            idx = [i for i, _, _ in batch]
+            images = transform([f.result() for f in cur])
+            res = forward(trainer, images, styles[idx], a2b, not output_only)
+            host = _to_host(res["bytes"]).numpy()                       # (P, B, H, W, 3): the one device->host copy of this batch
+            if tuple(host.shape[2:4]) != batch[0][2]:
+                raise L.AclganError("translate_folder: batch %d came back as %s for %s images" % (b, tuple(host.shape[2:4]), batch[0][2]))
+            for f in pending:                                           # the encodes of batch b-1 ran during this batch's forward
+                f.result()
+            pending = []
+            per = 2 if focus else 1
+            for k, (i, path, shape) in enumerate(batch):
+                o = paths[i]
+                for j in range(num_style):
+                    pending.append(pool.submit(_save, host[j * per, k], o["bar"][j]))
+                    if focus:
+                        pending.append(pool.submit(_save, host[j * per + 1, k], o["mask"][j]))
+                if o["input"]:
+                    pending.append(pool.submit(_save, host[num_style * per, k], o["input"]))
+                records.append((path, shape, b))
+                if keep_float:
+                    floats[path] = {"dec": [d[k].detach().cpu() for d in res["dec"]], "input": res["images"][k].detach().cpu()}
+        for f in pending:
+            f.result()
+    finally:
+        pool.shutdown(wait=True)
+    return (records, floats) if keep_float else records

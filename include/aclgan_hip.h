@@ -856,6 +856,27 @@ typedef struct aclgan_grid_src {
 size_t aclgan_image_grid_scratch_bytes(void);
 int aclgan_image_grid_u8(const aclgan_grid_src* srcs, int K, int H, int W, int nrow, uint8_t* out, void* scratch, void* stream);
 
+/* ---- finished pictures of a translated batch (csrc/finish.hip; what test_batch.py writes, reference test_batch.py:137-194) ----
+ * dec: decoder outputs (B, dec_channels, H, W) NCHW fp32, dec_channels 4 (image + focus plane) or 3; bg: the input images (B, 3, H, W).
+ * Every image's C*H*W block is contiguous; *_bstride = floats between consecutive images (>= 0), so batch slices and channel slices
+ * pass without a copy.  Up to three pictures per image, each written as (B, H, W, 3) HWC RGB bytes where its pointer is not NULL:
+ *   out_bar    4 channels: m = (f + 1) / 2, a = (fg + 1) / 2, b = (bg + 1) / 2, t = a * m + b * (1 - m), o = t * 2 - 1, u = (o + 1) / 2
+ *              (test.py's focus_translation, then its (o + 1) / 2); 3 channels: u = (dec + 1) / 2
+ *   out_mask   the focus plane as it is, in all three channels
+ *   out_input  bg as it is
+ * then save_image(padding=0, normalize=True) of ONE image, per picture and per image: lo / hi over that picture's own values, clamp,
+ * (x - lo) / d with d = fp32(double(hi) - double(lo) + 1e-5), * 255, + 0.5, clamp to [0, 255], truncation to uint8.  Every step above is
+ * one separately rounded fp32 operation (no contraction, a true division): the bytes equal the fp32 CPU evaluation exactly, and image
+ * i's bytes do not depend on B or on the other images of the batch.  lo / hi stay on the device as 2 x 3 x B integer keys (scratch:
+ * aclgan_translate_finish_scratch_bytes(B) bytes, 4-byte aligned, contents irrelevant); two launches on `stream`, no host
+ * synchronisation, no float picture stored.  NaN / Inf inputs do not fault; the pixels they produce are unspecified.
+ * ACLGAN_EINVAL, with nothing enqueued, for a null dec / scratch, no output at all, B, H or W < 1, dec_channels outside {3, 4}, bg == NULL
+ * with dec_channels 4 or with out_input, out_mask with dec_channels 3, a negative stride, B > 16384 or H * W > 2^28.
+ * aclgan_translate_finish_scratch_bytes launches nothing and needs no GPU (0 for B < 1). */
+size_t aclgan_translate_finish_scratch_bytes(int B);
+int aclgan_translate_finish_u8(const float* dec, int64_t dec_bstride, int dec_channels, const float* bg, int64_t bg_bstride, int B, int H, int W,
+                               uint8_t* out_bar, uint8_t* out_mask, uint8_t* out_input, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
