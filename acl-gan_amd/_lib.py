@@ -48,6 +48,10 @@ class ImageDesc(C.Structure):
         "src_h", "src_w", "res_h", "res_w", "crop_y", "crop_x", "flip", "tab_x", "tab_y", "ksize_x", "ksize_y")]
 
 
+class PasteDesc(C.Structure):
+    _fields_ = [("src_offset", C.c_int64), ("out_offset", C.c_int64), ("src_h", C.c_int), ("src_w", C.c_int)]
+
+
 GRID_MAX_SRCS = 16      # ACLGAN_GRID_MAX_SRCS
 
 
@@ -216,6 +220,8 @@ SIGNATURES = {
     "aclgan_image_grid_u8": (ci, [C.POINTER(GridSrc), ci, ci, ci, ci, vp, vp, vp]),
     "aclgan_translate_finish_scratch_bytes": (sz, [ci]),
     "aclgan_translate_finish_u8": (ci, [vp, i64, ci, vp, i64, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "aclgan_translate_pad": (ci, [vp, i64, ci, ci, ci, ci, ci, vp, vp]),
+    "aclgan_translate_paste_u8": (ci, [vp, i64, ci, vp, i64, ci, ci, ci, ci, ci, vp, i64, C.POINTER(PasteDesc), vp, vp, vp, i64, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

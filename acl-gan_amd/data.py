@@ -179,6 +179,12 @@ class GpuBatchTransform:
         dev = host.to(self.device, non_blocking=True)
         return {"descs": descs, "dev": dev, "o_desc": o_desc, "o_tab": o_tab, "n": n, "out_hw": out_hw}
 
+    @staticmethod
+    def sources(st):
+        """the staged source pixels of stage()'s state, for a later kernel that reads them again (translate.paste_u8): (the 1-D uint8
+        device buffer of the packed HWC RGB pixels, [(byte offset, src_h, src_w) per image])"""
+        return st["dev"][:st["o_desc"]], [(d.src_offset, d.src_h, d.src_w) for d in st["descs"]]
+
     def launch(self, st, stream=None):
         """device half: one kernel for the whole batch -> float32 [n][3][th][tw]"""
         th, tw = st["out_hw"]

@@ -2,7 +2,9 @@
 
 finish_u8         decoder outputs + input images of a batch -> the byte pictures that get written, on the device (csrc/finish.hip through
                   aclgan_translate_finish_u8: focus blend, one value range per picture per image, normalisation, rounding to bytes)
-translate_batch   one encode of the batch, one decode per style column, finish_u8; every byte of the batch in ONE device buffer
+reflect_pad       fit: pad -- a batch whose shape is no multiple of 2 ** n_downsample, padded at the bottom and the right (csrc/paste.hip)
+paste_u8          full_size -- the edit of a batch pasted onto every image's own source pixels, at the source's size (csrc/paste.hip)
+translate_batch   one encode of the batch, one decode per style column, finish_u8 or paste_u8; every byte of the batch in ONE device buffer
 translate_folder  the driver: file order, grouping by shape, style draws, output paths, one device->host copy per batch, Pillow encodes in a
                   thread pool while the next batch is decoded and translated
 
@@ -12,6 +14,7 @@ it -- is computed here per batch; with batch_size 1 the written files are byte-i
 import os
 from concurrent.futures import ThreadPoolExecutor
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -57,15 +60,98 @@ def finish_u8(dec, images=None, outputs=None, out=None, stream=None):
     return res
 
 
-def translate_batch(trainer, images, styles, a2b=True, with_input=True):
+def padded_shape(shape, multiple):
+    """(PH, PW): each side of (oh, ow) rounded up to the next multiple"""
+    return tuple(-(-n // multiple) * multiple for n in shape)
+
+
+def reflect_pad(images, multiple, stream=None):
+    """images (B, C, oh, ow) device fp32 -> (B, C, PH, PW), PH / PW the next multiples of `multiple`: rows added at the bottom and columns at
+    the right by reflection without the edge, copied bit for bit (include/aclgan_hip.h: aclgan_translate_pad).  A side below `multiple` is
+    an error.  One launch, also for a shape that is aligned already (a plain copy).  Nothing is synchronised."""
+    dev = images.device
+    if dev.type != "cuda":
+        raise L.AclganError("reflect_pad: tensors must be on the GPU (got %s); there is no CPU path" % dev)
+    if images.dim() != 4 or images.shape[0] < 1:
+        raise L.AclganError("reflect_pad: expected (B, C, H, W) images, got %s" % (tuple(images.shape),))
+    B, Cn, oh, ow = images.shape
+    with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        s = _dense(images)
+        PH, PW = padded_shape((oh, ow), multiple) if multiple >= 1 else (oh, ow)
+        out = torch.empty(B, Cn, PH, PW, dtype=torch.float32, device=dev)
+        L.check(L.lib.aclgan_translate_pad(L.ptr(s), s.stride(0) if B > 1 else 0, B, Cn, oh, ow, multiple, L.ptr(out), L.stream_ptr(dev)), "translate_pad")
+    return out
+
+
+def paste_plan(sources, device):
+    """sources: per image (byte offset of its HWC RGB uint8 pixels in the staged buffer, src_h, src_w).  Packs the pictures of the batch one
+    after the other and returns the descriptors of aclgan_translate_paste_u8 on the host and on `device`:
+    {'descs', 'dev', 'offsets': [byte offset of image k's picture], 'sizes': [(src_h, src_w)], 'total': bytes of one picture kind}"""
+    n = len(sources)
+    descs = (L.PasteDesc * n)()
+    offsets, sizes, off = [], [], 0
+    for k, (so, h, w) in enumerate(sources):
+        d = descs[k]
+        d.src_offset, d.out_offset, d.src_h, d.src_w = int(so), off, int(h), int(w)
+        offsets.append(off)
+        sizes.append((int(h), int(w)))
+        off += int(h) * int(w) * 3
+    host = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8)
+    if torch.device(device).type == "cuda":                # pinned: the copy is asynchronous, as the staging upload of the pixels is
+        host = host.pin_memory()
+    dev = host.to(device, non_blocking=True)
+    return {"descs": descs, "dev": dev, "offsets": offsets, "sizes": sizes, "total": off}
+
+
+def paste_u8(dec, x, valid, src, plan, outputs=("bar", "mask"), out=None, stream=None):
+    """The edit at every image's own size (include/aclgan_hip.h: aclgan_translate_paste_u8).  dec (B, 4 or 3, PH, PW) decoder outputs and
+    x (B, 3, PH, PW) the net input, device fp32 (batch and channel slices pass without a copy, as in finish_u8); valid = (oh, ow): the
+    region of them that is the resized source; src: the 1-D uint8 device buffer the sources were staged in (GpuBatchTransform.stage);
+    plan: paste_plan() of the batch.  out: optional dict of preallocated contiguous 1-D uint8 device tensors of plan['total'] bytes.
+    Returns {name: uint8 (total,)}: image k's (src_h, src_w, 3) picture starts at plan['offsets'][k].  Nothing is synchronised."""
+    dev = dec.device
+    if dev.type != "cuda":
+        raise L.AclganError("paste_u8: tensors must be on the GPU (got %s); there is no CPU path" % dev)
+    if dec.dim() != 4 or dec.shape[1] not in (3, 4) or dec.shape[0] < 1:
+        raise L.AclganError("paste_u8: expected a (B, 3 or 4, H, W) decoder output, got %s" % (tuple(dec.shape),))
+    B, Cd, PH, PW = dec.shape
+    if tuple(x.shape) != (B, 3, PH, PW) or x.device != dev:
+        raise L.AclganError("paste_u8: expected (%d, 3, %d, %d) net inputs on %s, got %s on %s" % (B, PH, PW, dev, tuple(x.shape), x.device))
+    oh, ow = valid
+    if len(plan["sizes"]) != B or src.dtype != torch.uint8 or src.dim() != 1 or src.device != dev or not src.is_contiguous():
+        raise L.AclganError("paste_u8: expected %d staged sources in a contiguous 1-D uint8 buffer on %s" % (B, dev))
+    outputs = list(outputs)
+    if not outputs or any(n not in ("bar", "mask") for n in outputs):
+        raise L.AclganError("paste_u8: outputs must be a non-empty subset of ('bar', 'mask'), got %s" % (outputs,))
+    with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        d, g = _dense(dec), _dense(x)
+        res = {}
+        for n in outputs:
+            t = out[n] if out is not None else torch.empty(plan["total"], dtype=torch.uint8, device=dev)
+            if tuple(t.shape) != (plan["total"],) or t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
+                raise L.AclganError("paste_u8: out[%r] must be a contiguous (%d,) uint8 tensor on %s" % (n, plan["total"], dev))
+            res[n] = t
+        L.check(L.lib.aclgan_translate_paste_u8(L.ptr(d), d.stride(0) if B > 1 else 0, Cd, L.ptr(g), g.stride(0) if B > 1 else 0, B, oh, ow, PH, PW,
+                                                L.ptr(src), src.numel(), plan["descs"], L.ptr(plan["dev"]), L.ptr(res.get("bar")),
+                                                L.ptr(res.get("mask")), plan["total"], L.stream_ptr(dev)), "translate_paste_u8")
+    return res
+
+
+def translate_batch(trainer, images, styles, a2b=True, with_input=True, multiple=None, sources=None):
     """reference test_batch.py:115,137-142 for a whole batch: ONE encode of images (B, 3, H, W), one decode per style column of styles
     (B, S, style_dim, 1, 1) -- every image has its own style rows -- and the pictures of all of them through finish_u8.
-    Reads the weights trainer.ema_weights() selects, as encode / decode do.  Returns a dict:
-      dec     list of S raw decoder outputs (B, output_dim, H, W)
-      images  the batch on the device
+    Reads the weights trainer.ema_weights() selects, as encode / decode do.
+    multiple (fit: pad): the images are reflect_pad()ded to multiples of it in front of the generators, and the pictures are finish_u8 of the
+    top-left (H, W) crop of the decoder output and of the net input -- strided views, which finish_u8 copies dense.
+    sources (full_size): (the staged uint8 device buffer, [(byte offset, src_h, src_w) per image]) -- bar and mask come from paste_u8 at
+    every image's own source size instead, packed; there is no input picture.  Returns a dict:
+      dec     list of S raw decoder outputs (B, output_dim, PH, PW): the net's shape, (H, W) unless padded
+      images  the net input (B, 3, PH, PW) on the device;  valid  (H, W)
       bar     list of S uint8 (B, H, W, 3);  mask  the same when the configuration has a focus channel, else None
       input   uint8 (B, H, W, 3), or None without with_input
-      bytes   the one uint8 device buffer (P, B, H, W, 3) all of those are views of, P = S (x 2 with masks) (+ 1 with the input)"""
+      bytes   the one uint8 device buffer (P, B, H, W, 3) all of those are views of, P = S (x 2 with masks) (+ 1 with the input)
+    with sources: bar / mask are lists of S uint8 (T,), bytes is (P, T), input None, and 'offsets' / 'sizes' say where image k's
+    (src_h, src_w, 3) picture lies in each."""
     gen = trainer.gen_AB if a2b else trainer.gen_BA
     focus = trainer.focus_lam > 0
     images = images.to(trainer.device, torch.float32)
@@ -76,19 +162,38 @@ def translate_batch(trainer, images, styles, a2b=True, with_input=True):
         raise L.AclganError("translate_batch: expected (%d, S, style_dim, 1, 1) styles, got %s" % (B, tuple(styles.shape)))
     S = styles.shape[1]
     styles = styles.to(trainer.device, torch.float32)
+    padded = multiple is not None and padded_shape((H, W), multiple) != (H, W)
     with torch.no_grad():
+        if padded:
+            images = reflect_pad(images, multiple)
         content, _ = gen.encode(images)
         per = 2 if focus else 1
-        buf = torch.empty(S * per + (1 if with_input else 0), B, H, W, 3, dtype=torch.uint8, device=trainer.device)
-        res = {"dec": [], "images": images, "bar": [], "mask": [] if focus else None, "input": buf[S * per] if with_input else None, "bytes": buf}
+        if sources is not None:
+            if len(sources[1]) != B:
+                raise L.AclganError("translate_batch: %d staged sources for %d images" % (len(sources[1]), B))
+            plan = paste_plan(sources[1], trainer.device)
+            buf = torch.empty(S * per, plan["total"], dtype=torch.uint8, device=trainer.device)
+            res = {"dec": [], "images": images, "valid": (H, W), "bar": [], "mask": [] if focus else None, "input": None, "bytes": buf,
+                   "offsets": plan["offsets"], "sizes": plan["sizes"]}
+        else:
+            buf = torch.empty(S * per + (1 if with_input else 0), B, H, W, 3, dtype=torch.uint8, device=trainer.device)
+            res = {"dec": [], "images": images, "valid": (H, W), "bar": [], "mask": [] if focus else None,
+                   "input": buf[S * per] if with_input else None, "bytes": buf}
         for j in range(S):
             dec = gen.decode(content, styles[:, j])
             out = {"bar": buf[j * per]}
             if focus:
                 out["mask"] = buf[j * per + 1]
-            if with_input and j == 0:
-                out["input"] = res["input"]
-            finish_u8(dec if focus else dec[:, :3], images, outputs=list(out), out=out)      # (test.py: outputs[:, :3] without a focus loss)
+            fdec = dec if focus else dec[:, :3]                                              # (test.py: outputs[:, :3] without a focus loss)
+            if sources is not None:
+                paste_u8(fdec, images, (H, W), sources[0], plan, outputs=list(out), out=out)
+            else:
+                if with_input and j == 0:
+                    out["input"] = res["input"]
+                if padded:
+                    finish_u8(fdec[:, :, :H, :W], images[:, :, :H, :W], outputs=list(out), out=out)
+                else:
+                    finish_u8(fdec, images, outputs=list(out), out=out)
             res["dec"].append(dec)
             res["bar"].append(out["bar"])
             if focus:
@@ -113,23 +218,34 @@ def image_size(path):
         return im.size
 
 
-def plan_batches(files, new_size, multiple, batch_size, size_of=image_size):
+FITS = ("refuse", "pad")
+
+
+def plan_batches(files, new_size, multiple, batch_size, size_of=image_size, fit="refuse"):
     """Consecutive files of equal resized shape form a batch of at most batch_size; a change of shape closes the batch.  Raises before
     anything runs for a file whose resized H or W is no multiple of `multiple` (2 ** gen.n_downsample: the decoder would return another size
-    than the encoder was given, and the blend with the input would fail).  Returns a list of batches, each a list of (index, path, (H, W))."""
+    than the encoder was given, and the blend with the input would fail) -- unless fit is 'pad': then the net input is the resized shape
+    with each side rounded up to the next multiple, and only a side below `multiple` is refused (reflection would need more than the image
+    holds).  Returns a list of batches, each a list of (index, path, (H, W), (PH, PW)): the resized shape and the net's."""
     if batch_size < 1:
         raise L.AclganError("translate_folder: batch_size must be positive, got %d" % batch_size)
+    if fit not in FITS:
+        raise L.AclganError("translate_folder: fit must be one of %s, got %r" % (FITS, fit))
     batches, cur = [], []
     for i, path in enumerate(files):
         w, h = size_of(path)
         ow, oh = resized_size(w, h, new_size)
-        if oh % multiple or ow % multiple:
+        if fit == "pad":
+            if oh < multiple or ow < multiple:
+                raise L.AclganError("translate_folder: %s is %dx%d (H x W) after Resize(%s); padding by reflection to multiples of %d needs "
+                                    "at least %d pixels a side" % (path, oh, ow, new_size, multiple, multiple))
+        elif oh % multiple or ow % multiple:
             raise L.AclganError("translate_folder: %s is %dx%d (H x W) after Resize(%s); the generators take multiples of %d"
                                 % (path, oh, ow, new_size, multiple))
         if cur and (cur[0][2] != (oh, ow) or len(cur) == batch_size):
             batches.append(cur)
             cur = []
-        cur.append((i, path, (oh, ow)))
+        cur.append((i, path, (oh, ow), padded_shape((oh, ow), multiple)))
     if cur:
         batches.append(cur)
     return batches
@@ -161,6 +277,10 @@ def _save(arr, path):
     Image.fromarray(arr).save(path)          # the format follows the extension, as in torchvision's save_image
 
 
+def _save_source(im, path):
+    _save(np.asarray(im, dtype=np.uint8), path)     # a decoded image (PIL or array) as the host array it is
+
+
 def _to_host(t):
     """one copy of a batch's bytes into pinned memory; the caller's stream has finished when it returns"""
     if not t.is_cuda:
@@ -172,13 +292,18 @@ def _to_host(t):
 
 
 def translate_folder(trainer, config, input_folder, output_folder, a2b=True, num_style=1, synchronized=False, output_only=False,
-                     batch_size=8, max_images=3000, keep_float=False, forward=None, transform=None):
+                     batch_size=8, max_images=3000, keep_float=False, forward=None, transform=None, fit="refuse", full_size=False):
     """The reference's test_batch.py loop.  Per input file <out>/_%02d_bar/<basename> for every style, <out>/_%02d_mask/<basename> when
     focus_loss > 0, <out>/input%03d.jpg unless output_only.  The passes whose saves the reference has commented out (_hat, _til) are not run.
     forward(trainer, images, styles, a2b, with_input) / transform(list of decoded images): the device halves (translate_batch and
     GpuBatchTransform(new_size, train=False, crop=False)); replaceable, so that the planning can be checked where there is no GPU.
-    Returns a list of (path, (H, W), batch index) records in folder order; with keep_float (for tests) a pair of that list and
-    {path: {'dec': [S tensors (C, H, W)], 'input': (3, H, W)}} on the host."""
+    fit: 'refuse' (a resized shape that is no multiple of 2 ** n_downsample raises by name) or 'pad' (it is padded by reflection in front of
+    the generators and the pictures are the crop; forward is given multiple=).  full_size: bar and mask are written at every source file's
+    own decoded size -- the edit pasted onto the source pixels -- and input%03d.jpg is the decoded source; the transform is then used
+    through its stage() / launch() halves and forward is given sources=transform.sources(staged state).  With both off the calls
+    are exactly those above.
+    Returns a list of (path, (H, W), batch index) records in folder order, (H, W) the resized shape; with keep_float (for tests) a pair of
+    that list and {path: {'dec': [S tensors (C, PH, PW)], 'input': (3, PH, PW), 'valid': (H, W)}} on the host, (PH, PW) the net's shape."""
     gen_cfg = config["gen"]
     focus = config["focus_loss"] > 0
     if "new_size" in config:
@@ -188,7 +313,8 @@ def translate_folder(trainer, config, input_folder, output_folder, a2b=True, num
     if num_style < 1:
         raise L.AclganError("translate_folder: num_style must be positive, got %d" % num_style)
     files = list_files(input_folder, max_images)
-    batches = plan_batches(files, new_size, 2 ** gen_cfg["n_downsample"], batch_size)
+    multiple = 2 ** gen_cfg["n_downsample"]
+    batches = plan_batches(files, new_size, multiple, batch_size, fit=fit)
     styles = draw_styles(len(files), num_style, gen_cfg["style_dim"], synchronized)
     if forward is None:
         forward = translate_batch
@@ -201,32 +327,55 @@ def translate_folder(trainer, config, input_folder, output_folder, a2b=True, num
     records, floats, pending = [], {}, []
     pool = ThreadPoolExecutor(max_workers=min(MAX_WORKERS, max(4, 2 * batch_size)))
     try:
-        decode = lambda b: [pool.submit(default_loader, p) for _, p, _ in batches[b]]
+        decode = lambda b: [pool.submit(default_loader, p) for _, p, _, _ in batches[b]]
         nxt = decode(0)
+        extra = {"multiple": multiple} if fit == "pad" else {}
         for b, batch in enumerate(batches):
             cur = nxt
             nxt = decode(b + 1) if b + 1 < len(batches) else None      # the decode of batch b+1 overlaps everything below
-            idx = [i for i, _, _ in batch]
-            images = transform([f.result() for f in cur])
-            res = forward(trainer, images, styles[idx], a2b, not output_only)
+            idx = [i for i, _, _, _ in batch]
+            decoded = [f.result() for f in cur]
+            if full_size:
+                if not all(hasattr(transform, n) for n in ("stage", "launch", "sources")):
+                    raise L.AclganError("translate_folder: full_size needs a transform with stage(), launch() and sources() (GpuBatchTransform)")
+                st = transform.stage(decoded)                           # the one upload: the paste reads the bytes the resize kernel reads
+                images = transform.launch(st)
+                extra["sources"] = transform.sources(st)
+                res = forward(trainer, images, styles[idx], a2b, False, **extra)
+            else:
+                images = transform(decoded)
+                res = forward(trainer, images, styles[idx], a2b, not output_only, **extra)
             host = _to_host(res["bytes"]).numpy()                       # (P, B, H, W, 3): the one device->host copy of this batch
-            if tuple(host.shape[2:4]) != batch[0][2]:
+            if full_size:                                               # (P, T): every picture at its source's size, packed
+                sizes = [(h, w) for _, h, w in extra["sources"][1]]
+                if host.ndim != 2 or list(res["sizes"]) != sizes:
+                    raise L.AclganError("translate_folder: batch %d came back as %s for sources of %s" % (b, res.get("sizes"), sizes))
+            elif tuple(host.shape[2:4]) != batch[0][2]:
                 raise L.AclganError("translate_folder: batch %d came back as %s for %s images" % (b, tuple(host.shape[2:4]), batch[0][2]))
             for f in pending:                                           # the encodes of batch b-1 ran during this batch's forward
                 f.result()
             pending = []
             per = 2 if focus else 1
-            for k, (i, path, shape) in enumerate(batch):
+            for k, (i, path, shape, _) in enumerate(batch):
                 o = paths[i]
+                if full_size:
+                    (hs, ws), off = sizes[k], res["offsets"][k]
+                    pic = lambda p: host[p, off:off + hs * ws * 3].reshape(hs, ws, 3)
+                else:
+                    pic = lambda p: host[p, k]
                 for j in range(num_style):
-                    pending.append(pool.submit(_save, host[j * per, k], o["bar"][j]))
+                    pending.append(pool.submit(_save, pic(j * per), o["bar"][j]))
                     if focus:
-                        pending.append(pool.submit(_save, host[j * per + 1, k], o["mask"][j]))
+                        pending.append(pool.submit(_save, pic(j * per + 1), o["mask"][j]))
                 if o["input"]:
-                    pending.append(pool.submit(_save, host[num_style * per, k], o["input"]))
+                    if full_size:                                       # the decoded source as it is, from the host array
+                        pending.append(pool.submit(_save_source, decoded[k], o["input"]))
+                    else:
+                        pending.append(pool.submit(_save, pic(num_style * per), o["input"]))
                 records.append((path, shape, b))
                 if keep_float:
-                    floats[path] = {"dec": [d[k].detach().cpu() for d in res["dec"]], "input": res["images"][k].detach().cpu()}
+                    floats[path] = {"dec": [d[k].detach().cpu() for d in res["dec"]], "input": res["images"][k].detach().cpu(),
+                                    "valid": tuple(res.get("valid", shape))}
         for f in pending:
             f.result()
     finally:

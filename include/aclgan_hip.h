@@ -877,6 +877,47 @@ size_t aclgan_translate_finish_scratch_bytes(int B);
 int aclgan_translate_finish_u8(const float* dec, int64_t dec_bstride, int dec_channels, const float* bg, int64_t bg_bstride, int B, int H, int W,
                                uint8_t* out_bar, uint8_t* out_mask, uint8_t* out_input, void* scratch, void* stream);
 
+/* ---- photographs of any shape (csrc/paste.hip; translate_photos.py --fit pad / --full_size) ----
+ * aclgan_translate_pad: src (B, C, oh, ow) NCHW fp32, every image's C*oh*ow block contiguous, src_bstride floats between consecutive images
+ * (>= 0) -> dst (B, C, PH, PW) dense, PH / PW = oh / ow rounded up to the next multiple of `multiple` (2 ** n_downsample).  New rows go at
+ * the bottom and new columns at the right, by reflection without repeating the edge: row i >= oh is row 2 (oh - 1) - i, columns likewise;
+ * every value is copied as its 32 bits.  One launch on `stream`.  ACLGAN_EINVAL, with nothing enqueued, for a null pointer, B, C, oh, ow or
+ * multiple < 1, a side below `multiple` (reflection would need more than the image holds), a negative stride, B * C > 65535, a side above
+ * 2^22 or oh * ow > 2^28. */
+int aclgan_translate_pad(const float* src, int64_t src_bstride, int B, int C, int oh, int ow, int multiple, float* dst, void* stream);
+
+/* aclgan_translate_paste_u8: the edit of a translated batch at every image's own source size.  dec (B, dec_channels, PH, PW), dec_channels
+ * 4 (image + focus plane f) or 3, and x (B, 3, PH, PW), the net input, as in aclgan_translate_finish_u8 (*_bstride floats between images,
+ * >= 0); only their top-left (oh, ow) region -- the resized source -- is read, never the padded rows and columns.  One descriptor per image,
+ * on the host (validated here) and on the device (read by the kernel), mirroring aclgan_image_desc -- the two copies MUST be identical:
+ * the device copy cannot be checked here, and the kernel reads and writes where it says: the image's HWC RGB uint8 source pixels
+ * start src_offset bytes into `src` (the staging buffer aclgan_image_batch_transform has read; src_bytes long) and its (src_h, src_w, 3)
+ * pictures out_offset bytes into out_bar and out_mask (each out_bytes long; either may be NULL).  Every numbered step below is one
+ * separately rounded fp32 operation (no contraction, true divisions).  Residual at net resolution, recomputed at every tap (no float
+ * picture is stored):
+ *   m = (f + 1) * 0.5   (dec_channels 3: m = 1),   r_c = m * ((fg_c - x_c) * 0.5)
+ * Sampling for output pixel (Y, X): bilinear, half-pixel centres, per axis with n_in = oh / ow and n_out = src_h / src_w
+ *   scale = fp32(n_in) / fp32(n_out), s = (fp32(Y) + 0.5) * scale, s = s - 0.5, s = max(s, 0), i0 = min(int(s), n_in - 1),
+ *   i1 = min(i0 + 1, n_in - 1), w = s - fp32(i0)
+ *   R = (1 - wy) * ((1 - wx) * r[y0][x0] + wx * r[y0][x1]) + wy * ((1 - wx) * r[y1][x0] + wx * r[y1][x1])
+ * Bytes: out_bar  t = R * 255, v = fp32(source byte) + t, v = v + 0.5, clamp to [0, 255], truncation;
+ *        out_mask the same interpolation M of m, M * 255, + 0.5, clamp, truncation, in all three channels.
+ * There is no normalize=True stretch: a pixel whose interpolated residual is 0 comes back as the source byte, so a closed mask (f = -1)
+ * returns the source; with (src_h, src_w) == (oh, ow) the weights are exactly 0 or 1; image i's bytes do not depend on B or on the other
+ * images.  The bytes equal the fp32 CPU evaluation of the rule exactly.  One launch on `stream`, no host synchronisation.  NaN / Inf inputs
+ * do not fault; the pixels they produce are unspecified.
+ * ACLGAN_EINVAL, with nothing enqueued, for a null dec / x / src / descriptor array, no output at all, B, oh or ow < 1, PH < oh or PW < ow,
+ * dec_channels outside {3, 4}, a negative stride, B > 16384, a side above 2^22 or more than 2^28 pixels (planes or a source), a source size
+ * < 1, source bytes that run past src_bytes, output offsets that do not ascend without overlap or run past out_bytes. */
+typedef struct aclgan_paste_desc {
+    int64_t src_offset;      /* byte offset of this image's HWC RGB uint8 source pixels in `src` */
+    int64_t out_offset;      /* byte offset of this image's (src_h, src_w, 3) picture in out_bar and in out_mask */
+    int src_h, src_w;        /* decoded size */
+} aclgan_paste_desc;
+int aclgan_translate_paste_u8(const float* dec, int64_t dec_bstride, int dec_channels, const float* x, int64_t x_bstride, int B, int oh, int ow, int PH,
+                              int PW, const void* src, int64_t src_bytes, const aclgan_paste_desc* descs_host, const void* descs_dev,
+                              uint8_t* out_bar, uint8_t* out_mask, int64_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
