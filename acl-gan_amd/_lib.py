@@ -222,6 +222,9 @@ SIGNATURES = {
     "aclgan_translate_finish_u8": (ci, [vp, i64, ci, vp, i64, ci, ci, ci, vp, vp, vp, vp, vp]),
     "aclgan_translate_pad": (ci, [vp, i64, ci, ci, ci, ci, ci, vp, vp]),
     "aclgan_translate_paste_u8": (ci, [vp, i64, ci, vp, i64, ci, ci, ci, ci, ci, vp, i64, C.POINTER(PasteDesc), vp, vp, vp, i64, vp]),
+    "aclgan_translate_guided_scratch_bytes": (sz, [ci, ci, ci, ci]),
+    "aclgan_translate_guided_coef": (ci, [vp, i64, ci, vp, i64, ci, ci, ci, ci, ci, ci, C.c_float, vp, vp, vp]),
+    "aclgan_translate_guided_paste_u8": (ci, [vp, ci, ci, ci, ci, vp, i64, C.POINTER(PasteDesc), vp, vp, vp, i64, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -43,6 +43,15 @@ int colsum_ordered(const float* dy, float* db, int64_t M, int C, void* part, hip
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// what a batch pasted at its sources' sizes must satisfy whichever kernel writes it (paste.hip; aclgan_translate_paste_u8 and
+// aclgan_translate_guided_paste_u8 of guided.hip): the staged source, the outputs and every host descriptor.  ACLGAN_EINVAL with the error
+// set in `who`'s name, else ACLGAN_OK and *grid_x = the workgroups along x that the tallest image needs (4 pixels per lane, 256 lanes).
+constexpr int PASTE_MAX_BATCH = 16384;       // images along gridDim.y
+constexpr int PASTE_MAX_SIDE = 1 << 22;      // fp32(Y) + 0.5 is exact below 2^23
+constexpr int64_t PASTE_MAX_PIXELS = (int64_t)1 << 28;
+int paste_check_batch(const char* who, int B, const void* src, int64_t src_bytes, const aclgan_paste_desc* descs_host, const void* descs_dev,
+                      const void* out_bar, const void* out_mask, int64_t out_bytes, int* grid_x);
+
 // geometry derived from a conv descriptor
 struct ConvGeom {
     int B, Hi, Wi, Ci, Co, k, s, p, up, act;

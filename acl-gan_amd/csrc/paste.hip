@@ -31,10 +31,10 @@
 namespace aclgan {
 namespace {
 
-constexpr int MAX_BATCH = 16384;       // images along gridDim.y
+constexpr int MAX_BATCH = PASTE_MAX_BATCH;
 constexpr int MAX_GX = 256;            // workgroups per image; the rest by grid stride
-constexpr int MAX_SIDE = 1 << 22;      // fp32(Y) + 0.5 is exact below 2^23
-constexpr int64_t MAX_PIXELS = (int64_t)1 << 28;
+constexpr int MAX_SIDE = PASTE_MAX_SIDE;
+constexpr int64_t MAX_PIXELS = PASTE_MAX_PIXELS;
 
 struct PasteArgs {                     // passed by value as a kernel argument
     const float* dec;
@@ -216,6 +216,36 @@ __global__ void __launch_bounds__(256) reflect_pad_kernel(const uint32_t* __rest
 }
 
 }  // namespace
+
+int paste_check_batch(const char* who, int B, const void* src, int64_t src_bytes, const aclgan_paste_desc* descs_host, const void* descs_dev,
+                      const void* out_bar, const void* out_mask, int64_t out_bytes, int* grid_x) {
+    ACL_REQUIRE(src && descs_host && descs_dev, "%s: null pointer", who);
+    ACL_REQUIRE(out_bar || out_mask, "%s: no output asked for", who);
+    ACL_REQUIRE(B > 0 && B <= MAX_BATCH, "%s: %d images (1 to %d)", who, B, MAX_BATCH);
+    ACL_REQUIRE(src_bytes > 0 && out_bytes > 0, "%s: empty source or output buffer", who);
+    int64_t end = 0;
+    int gx = 1;
+    for (int i = 0; i < B; ++i) {
+        const aclgan_paste_desc& d = descs_host[i];
+        ACL_REQUIRE(d.src_h > 0 && d.src_w > 0, "%s: image %d: non-positive source size %dx%d", who, i, d.src_h, d.src_w);
+        ACL_REQUIRE(d.src_h <= MAX_SIDE && d.src_w <= MAX_SIDE && (int64_t)d.src_h * d.src_w <= MAX_PIXELS, "%s: image %d: a %dx%d source is too large",
+                    who, i, d.src_h, d.src_w);
+        const int64_t n = (int64_t)d.src_h * d.src_w * 3;
+        ACL_REQUIRE(d.src_offset >= 0 && d.src_offset <= src_bytes - n, "%s: image %d: source bytes [%lld, +%lld) run past the %lld of the buffer", who, i,
+                    (long long)d.src_offset, (long long)n, (long long)src_bytes);
+        ACL_REQUIRE(d.out_offset >= end, "%s: image %d: output offset %lld overlaps the picture before it (offsets ascend)", who, i,
+                    (long long)d.out_offset);
+        ACL_REQUIRE(d.out_offset <= out_bytes - n, "%s: image %d: output bytes [%lld, +%lld) run past the %lld of the buffer", who, i,
+                    (long long)d.out_offset, (long long)n, (long long)out_bytes);
+        end = d.out_offset + n;
+        int tx_log2 = 0;
+        while (tx_log2 < 8 && (1 << tx_log2) < (d.src_w + 3) / 4) ++tx_log2;
+        gx = std::max(gx, std::min(cdiv(d.src_h, 256 >> tx_log2), MAX_GX));
+    }
+    *grid_x = gx;
+    return ACLGAN_OK;
+}
+
 }  // namespace aclgan
 
 using namespace aclgan;
@@ -244,34 +274,14 @@ int aclgan_translate_pad(const float* src, int64_t src_bstride, int B, int C, in
 int aclgan_translate_paste_u8(const float* dec, int64_t dec_bstride, int dec_channels, const float* x, int64_t x_bstride, int B, int oh, int ow, int PH,
                               int PW, const void* src, int64_t src_bytes, const aclgan_paste_desc* descs_host, const void* descs_dev,
                               uint8_t* out_bar, uint8_t* out_mask, int64_t out_bytes, void* stream) {
-    ACL_REQUIRE(dec && x && src && descs_host && descs_dev, "translate_paste_u8: null pointer");
-    ACL_REQUIRE(out_bar || out_mask, "translate_paste_u8: no output asked for");
+    ACL_REQUIRE(dec && x, "translate_paste_u8: null pointer");
     ACL_REQUIRE(B > 0 && oh > 0 && ow > 0, "translate_paste_u8: B, oh, ow must be positive (%d, %d, %d)", B, oh, ow);
     ACL_REQUIRE(PH >= oh && PW >= ow, "translate_paste_u8: the valid region %dx%d does not fit the planes %dx%d", oh, ow, PH, PW);
     ACL_REQUIRE(dec_channels == 3 || dec_channels == 4, "translate_paste_u8: a decoder output of %d channels (3 or 4)", dec_channels);
-    ACL_REQUIRE(B <= MAX_BATCH, "translate_paste_u8: %d images (at most %d)", B, MAX_BATCH);
     ACL_REQUIRE(PH <= MAX_SIDE && PW <= MAX_SIDE && (int64_t)PH * PW <= MAX_PIXELS, "translate_paste_u8: %dx%d planes are too large", PH, PW);
     ACL_REQUIRE(dec_bstride >= 0 && x_bstride >= 0, "translate_paste_u8: negative batch stride");
-    ACL_REQUIRE(src_bytes > 0 && out_bytes > 0, "translate_paste_u8: empty source or output buffer");
-    int64_t end = 0;
     int gx = 1;
-    for (int i = 0; i < B; ++i) {
-        const aclgan_paste_desc& d = descs_host[i];
-        ACL_REQUIRE(d.src_h > 0 && d.src_w > 0, "translate_paste_u8: image %d: non-positive source size %dx%d", i, d.src_h, d.src_w);
-        ACL_REQUIRE(d.src_h <= MAX_SIDE && d.src_w <= MAX_SIDE && (int64_t)d.src_h * d.src_w <= MAX_PIXELS,
-                    "translate_paste_u8: image %d: a %dx%d source is too large", i, d.src_h, d.src_w);
-        const int64_t n = (int64_t)d.src_h * d.src_w * 3;
-        ACL_REQUIRE(d.src_offset >= 0 && d.src_offset <= src_bytes - n, "translate_paste_u8: image %d: source bytes [%lld, +%lld) run past the %lld of the buffer",
-                    i, (long long)d.src_offset, (long long)n, (long long)src_bytes);
-        ACL_REQUIRE(d.out_offset >= end, "translate_paste_u8: image %d: output offset %lld overlaps the picture before it (offsets ascend)", i,
-                    (long long)d.out_offset);
-        ACL_REQUIRE(d.out_offset <= out_bytes - n, "translate_paste_u8: image %d: output bytes [%lld, +%lld) run past the %lld of the buffer", i,
-                    (long long)d.out_offset, (long long)n, (long long)out_bytes);
-        end = d.out_offset + n;
-        int tx_log2 = 0;
-        while (tx_log2 < 8 && (1 << tx_log2) < (d.src_w + 3) / 4) ++tx_log2;
-        gx = std::max(gx, std::min(cdiv(d.src_h, 256 >> tx_log2), MAX_GX));
-    }
+    if (const int rc = paste_check_batch("translate_paste_u8", B, src, src_bytes, descs_host, descs_dev, out_bar, out_mask, out_bytes, &gx)) return rc;
     PasteArgs a = {};
     a.dec = dec; a.x = x; a.dec_bs = dec_bstride; a.x_bs = x_bstride;
     a.plane = (int64_t)PH * PW;

@@ -4,7 +4,10 @@ finish_u8         decoder outputs + input images of a batch -> the byte pictures
                   aclgan_translate_finish_u8: focus blend, one value range per picture per image, normalisation, rounding to bytes)
 reflect_pad       fit: pad -- a batch whose shape is no multiple of 2 ** n_downsample, padded at the bottom and the right (csrc/paste.hip)
 paste_u8          full_size -- the edit of a batch pasted onto every image's own source pixels, at the source's size (csrc/paste.hip)
-translate_batch   one encode of the batch, one decode per style column, finish_u8 or paste_u8; every byte of the batch in ONE device buffer
+guided_u8         full_size, detail: guided -- the same pictures with the photograph's own detail inside the edit: a local affine model of
+                  the edit fitted at net resolution, upsampled and evaluated on the source pixels (csrc/guided.hip)
+translate_batch   one encode of the batch, one decode per style column, finish_u8, paste_u8 or guided_u8; every byte of the batch in ONE
+                  device buffer
 translate_folder  the driver: file order, grouping by shape, style draws, output paths, one device->host copy per batch, Pillow encodes in a
                   thread pool while the next batch is decoded and translated
 
@@ -137,7 +140,55 @@ def paste_u8(dec, x, valid, src, plan, outputs=("bar", "mask"), out=None, stream
     return res
 
 
-def translate_batch(trainer, images, styles, a2b=True, with_input=True, multiple=None, sources=None):
+DETAILS = ("bilinear", "guided")
+GUIDED_RADIUS, GUIDED_EPS = 4, 1e-3          # this project's choice: nobody has measured which values suit the datasets
+
+
+def guided_u8(dec, x, valid, src, plan, radius=GUIDED_RADIUS, eps=GUIDED_EPS, outputs=("bar", "mask"), out=None, stream=None):
+    """paste_u8's pictures by guided-filter upsampling (include/aclgan_hip.h: aclgan_translate_guided_coef, aclgan_translate_guided_paste_u8):
+    per window of radius `radius` and per channel an affine model of the residual in the net input is fitted at net resolution
+    (regularised by eps), its smoothed coefficients are upsampled and evaluated on the source bytes.  Arguments, outputs and layout are
+    paste_u8's; radius is an integer in [1, 16], eps lies in [1e-6, 1].  The coefficient planes (B, 7 or 6, oh, ow) and the scratch are
+    allocated here; three launches.  Nothing is synchronised."""
+    dev = dec.device
+    if dev.type != "cuda":
+        raise L.AclganError("guided_u8: tensors must be on the GPU (got %s); there is no CPU path" % dev)
+    if dec.dim() != 4 or dec.shape[1] not in (3, 4) or dec.shape[0] < 1:
+        raise L.AclganError("guided_u8: expected a (B, 3 or 4, H, W) decoder output, got %s" % (tuple(dec.shape),))
+    B, Cd, PH, PW = dec.shape
+    if tuple(x.shape) != (B, 3, PH, PW) or x.device != dev:
+        raise L.AclganError("guided_u8: expected (%d, 3, %d, %d) net inputs on %s, got %s on %s" % (B, PH, PW, dev, tuple(x.shape), x.device))
+    oh, ow = valid
+    if len(plan["sizes"]) != B or src.dtype != torch.uint8 or src.dim() != 1 or src.device != dev or not src.is_contiguous():
+        raise L.AclganError("guided_u8: expected %d staged sources in a contiguous 1-D uint8 buffer on %s" % (B, dev))
+    outputs = list(outputs)
+    if not outputs or any(n not in ("bar", "mask") for n in outputs):
+        raise L.AclganError("guided_u8: outputs must be a non-empty subset of ('bar', 'mask'), got %s" % (outputs,))
+    if "mask" in outputs and Cd == 3:
+        raise L.AclganError("guided_u8: the mask picture needs the m plane, which a 3-channel decoder output does not give")
+    if int(radius) != radius:
+        raise L.AclganError("guided_u8: radius must be an integer, got %r" % (radius,))
+    radius, planes = int(radius), 7 if Cd == 4 else 6
+    with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        d, g = _dense(dec), _dense(x)
+        res = {}
+        for n in outputs:
+            t = out[n] if out is not None else torch.empty(plan["total"], dtype=torch.uint8, device=dev)
+            if tuple(t.shape) != (plan["total"],) or t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
+                raise L.AclganError("guided_u8: out[%r] must be a contiguous (%d,) uint8 tensor on %s" % (n, plan["total"], dev))
+            res[n] = t
+        coef = torch.empty(B, planes, max(oh, 0), max(ow, 0), dtype=torch.float32, device=dev)
+        scratch = torch.empty(max(L.lib.aclgan_translate_guided_scratch_bytes(B, oh, ow, radius), 4), dtype=torch.uint8, device=dev)
+        L.check(L.lib.aclgan_translate_guided_coef(L.ptr(d), d.stride(0) if B > 1 else 0, Cd, L.ptr(g), g.stride(0) if B > 1 else 0, B, oh, ow, PH, PW,
+                                                   radius, eps, L.ptr(coef), L.ptr(scratch), L.stream_ptr(dev)), "translate_guided_coef")
+        L.check(L.lib.aclgan_translate_guided_paste_u8(L.ptr(coef), planes, B, oh, ow, L.ptr(src), src.numel(), plan["descs"], L.ptr(plan["dev"]),
+                                                       L.ptr(res.get("bar")), L.ptr(res.get("mask")), plan["total"], L.stream_ptr(dev)),
+                "translate_guided_paste_u8")
+    return res
+
+
+def translate_batch(trainer, images, styles, a2b=True, with_input=True, multiple=None, sources=None, detail=None, guided_radius=GUIDED_RADIUS,
+                    guided_eps=GUIDED_EPS):
     """reference test_batch.py:115,137-142 for a whole batch: ONE encode of images (B, 3, H, W), one decode per style column of styles
     (B, S, style_dim, 1, 1) -- every image has its own style rows -- and the pictures of all of them through finish_u8.
     Reads the weights trainer.ema_weights() selects, as encode / decode do.
@@ -151,7 +202,12 @@ def translate_batch(trainer, images, styles, a2b=True, with_input=True, multiple
       input   uint8 (B, H, W, 3), or None without with_input
       bytes   the one uint8 device buffer (P, B, H, W, 3) all of those are views of, P = S (x 2 with masks) (+ 1 with the input)
     with sources: bar / mask are lists of S uint8 (T,), bytes is (P, T), input None, and 'offsets' / 'sizes' say where image k's
-    (src_h, src_w, 3) picture lies in each."""
+    (src_h, src_w, 3) picture lies in each.
+    detail (with sources only): None or 'bilinear' -- paste_u8 -- or 'guided' -- guided_u8(radius=guided_radius, eps=guided_eps)."""
+    if detail not in (None,) + DETAILS:
+        raise L.AclganError("translate_batch: detail must be one of %s, got %r" % (DETAILS, detail))
+    if detail == "guided" and sources is None:
+        raise L.AclganError("translate_batch: detail='guided' upsamples the edit to the staged sources' size; without sources there is nothing to upsample")
     gen = trainer.gen_AB if a2b else trainer.gen_BA
     focus = trainer.focus_lam > 0
     images = images.to(trainer.device, torch.float32)
@@ -185,7 +241,9 @@ def translate_batch(trainer, images, styles, a2b=True, with_input=True, multiple
             if focus:
                 out["mask"] = buf[j * per + 1]
             fdec = dec if focus else dec[:, :3]                                              # (test.py: outputs[:, :3] without a focus loss)
-            if sources is not None:
+            if sources is not None and detail == "guided":
+                guided_u8(fdec, images, (H, W), sources[0], plan, radius=guided_radius, eps=guided_eps, outputs=list(out), out=out)
+            elif sources is not None:
                 paste_u8(fdec, images, (H, W), sources[0], plan, outputs=list(out), out=out)
             else:
                 if with_input and j == 0:
@@ -292,7 +350,8 @@ def _to_host(t):
 
 
 def translate_folder(trainer, config, input_folder, output_folder, a2b=True, num_style=1, synchronized=False, output_only=False,
-                     batch_size=8, max_images=3000, keep_float=False, forward=None, transform=None, fit="refuse", full_size=False):
+                     batch_size=8, max_images=3000, keep_float=False, forward=None, transform=None, fit="refuse", full_size=False,
+                     detail="bilinear", guided_radius=GUIDED_RADIUS, guided_eps=GUIDED_EPS):
     """The reference's test_batch.py loop.  Per input file <out>/_%02d_bar/<basename> for every style, <out>/_%02d_mask/<basename> when
     focus_loss > 0, <out>/input%03d.jpg unless output_only.  The passes whose saves the reference has commented out (_hat, _til) are not run.
     forward(trainer, images, styles, a2b, with_input) / transform(list of decoded images): the device halves (translate_batch and
@@ -302,6 +361,9 @@ def translate_folder(trainer, config, input_folder, output_folder, a2b=True, num
     own decoded size -- the edit pasted onto the source pixels -- and input%03d.jpg is the decoded source; the transform is then used
     through its stage() / launch() halves and forward is given sources=transform.sources(staged state).  With both off the calls
     are exactly those above.
+    detail: how the edit reaches the source's size under full_size -- 'bilinear' (the residual interpolated: paste_u8; forward is given no
+    further keyword) or 'guided' (guided_u8 with guided_radius and guided_eps: forward is given detail=, guided_radius=, guided_eps=).
+    'guided' without full_size is refused: the pictures are then written at the net's size, and there is nothing to upsample.
     Returns a list of (path, (H, W), batch index) records in folder order, (H, W) the resized shape; with keep_float (for tests) a pair of
     that list and {path: {'dec': [S tensors (C, PH, PW)], 'input': (3, PH, PW), 'valid': (H, W)}} on the host, (PH, PW) the net's shape."""
     gen_cfg = config["gen"]
@@ -312,6 +374,11 @@ def translate_folder(trainer, config, input_folder, output_folder, a2b=True, num
         new_size = config["new_size_a"] if a2b else config["new_size_b"]
     if num_style < 1:
         raise L.AclganError("translate_folder: num_style must be positive, got %d" % num_style)
+    if detail not in DETAILS:
+        raise L.AclganError("translate_folder: detail must be one of %s, got %r" % (DETAILS, detail))
+    if detail == "guided" and not full_size:
+        raise L.AclganError("translate_folder: detail='guided' needs full_size: without it the pictures are written at the net's size, "
+                            "and there is nothing to upsample")
     files = list_files(input_folder, max_images)
     multiple = 2 ** gen_cfg["n_downsample"]
     batches = plan_batches(files, new_size, multiple, batch_size, fit=fit)
@@ -330,6 +397,8 @@ def translate_folder(trainer, config, input_folder, output_folder, a2b=True, num
         decode = lambda b: [pool.submit(default_loader, p) for _, p, _, _ in batches[b]]
         nxt = decode(0)
         extra = {"multiple": multiple} if fit == "pad" else {}
+        if detail == "guided":
+            extra.update(detail="guided", guided_radius=guided_radius, guided_eps=guided_eps)
         for b, batch in enumerate(batches):
             cur = nxt
             nxt = decode(b + 1) if b + 1 < len(batches) else None      # the decode of batch b+1 overlaps everything below

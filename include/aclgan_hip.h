@@ -918,6 +918,41 @@ int aclgan_translate_paste_u8(const float* dec, int64_t dec_bstride, int dec_cha
                               int PW, const void* src, int64_t src_bytes, const aclgan_paste_desc* descs_host, const void* descs_dev,
                               uint8_t* out_bar, uint8_t* out_mask, int64_t out_bytes, void* stream);
 
+/* ---- the edit at source size with the photograph's own detail (csrc/guided.hip; translate_photos.py --full_size --detail guided) ----
+ * The fast guided filter (He & Sun 2015) in place of the bilinear blow-up of the residual: at net resolution a local affine model
+ * r ~ a g + b from the net input g to the residual r is fitted per window and channel, a and b are smoothed, and THEY are upsampled and
+ * evaluated on the source bytes.  Where the edit is locally an affine function of the input, detail above the net's resolution passes
+ * through it; where the residual is zero, a = b = 0 and the source byte comes back.  dec, x, (oh, ow), (PH, PW), the strides, the
+ * descriptors and the outputs are those of aclgan_translate_paste_u8; radius is an integer in [1, 16], eps lies in [1e-6, 1] (below that the
+ * cancellation in var leaves the fp32 rule nothing).  Every numbered operation is one separately rounded fp32 operation (no contraction,
+ * true divisions).
+ * At net resolution, over the valid (oh, ow) region only -- the padding is never read:
+ *   1. m = (f + 1) * 0.5 (dec_channels 3: m = 1), r_c = m * ((fg_c - x_c) * 0.5) as in the paste; the guide g_c = (x_c + 1) * 0.5;
+ *      gg_c = g_c * g_c, gr_c = g_c * r_c
+ *   2. box sum of a plane v, the window clipped to the region: h[i][j] = ((0 + v[i][j-radius]) + v[i][j-radius+1]) + ... + v[i][j+radius]
+ *      in ascending j, taps outside the region left out; s[i][j] the same over h[i-radius .. i+radius][j] in ascending i;
+ *      n = fp32(ny * nx), the number of taps inside; mean = s / n
+ *   3. per channel from the means Mg, Mr, Mgg, Mgr:  var = max(Mgg - Mg * Mg, 0), cov = Mgr - Mg * Mr, a = cov / (var + eps), b = Mr - a * Mg
+ *   4. A_c = mean(a_c), Bq_c = mean(b_c) by the same box
+ * At source resolution, per output pixel (Y, X) and channel:
+ *   5. the taps, weights and association of aclgan_translate_paste_u8's sampling rule, applied to A_c and Bq_c (and to m for the mask picture)
+ *   6. out_bar: G = fp32(byte) * fp32(1/255), E = A * G, E = E + Bq, t = E * 255, v = fp32(byte) + t, v = v + 0.5, clamp to [0, 255], truncation
+ *   7. out_mask: aclgan_translate_paste_u8's mask rule; its bytes equal that function's
+ * aclgan_translate_guided_coef runs 1-4 and writes coef, dense (B, 7, oh, ow) floats on the device: A_0..2, Bq_0..2, m -- (B, 6, oh, ow)
+ * without the m plane when dec_channels is 3.  Two launches on `stream`, no host synchronisation; scratch is the caller's,
+ * aclgan_translate_guided_scratch_bytes(B, oh, ow, radius) bytes, 4-byte aligned, contents irrelevant (the query launches nothing, needs no
+ * GPU and returns 0 for arguments the call would refuse).  aclgan_translate_guided_paste_u8 runs 5-7 from coef (coef_planes 7 or 6): one
+ * launch on `stream` for the whole batch of different source sizes.  The bytes and the coefficient planes equal the fp32 CPU evaluation of
+ * the rule exactly; image i's do not depend on B or on the other images.  NaN / Inf inputs do not fault; what they produce is unspecified.
+ * ACLGAN_EINVAL, with nothing enqueued, for everything aclgan_translate_paste_u8 refuses of the same arguments, a null coef or scratch, a
+ * radius or eps outside the ranges above (NaN included), coef_planes outside {6, 7}, and out_mask asked for from 6 planes. */
+size_t aclgan_translate_guided_scratch_bytes(int B, int oh, int ow, int radius);
+int aclgan_translate_guided_coef(const float* dec, int64_t dec_bstride, int dec_channels, const float* x, int64_t x_bstride, int B, int oh, int ow, int PH,
+                                 int PW, int radius, float eps, float* coef, void* scratch, void* stream);
+int aclgan_translate_guided_paste_u8(const float* coef, int coef_planes, int B, int oh, int ow, const void* src, int64_t src_bytes,
+                                     const aclgan_paste_desc* descs_host, const void* descs_dev, uint8_t* out_bar, uint8_t* out_mask, int64_t out_bytes,
+                                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
