@@ -469,7 +469,7 @@ int aclgan_avgpool3s2_bwd(int B, int H, int W, int C, const float* dy, float* dx
 }
 int aclgan_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* opt, int step, void* stream) {
     ACL_REQUIRE(p && g && m && v && opt, "adam: null buffer");
-    return adam_flat(p, g, m, v, n, opt, step, (hipStream_t)stream);
+    return adam_update({p, g, m, v, n, opt, step}, (hipStream_t)stream);
 }
 int aclgan_grad_clip_flat(const float* g, int64_t n, float max_norm, float* state, void* stream) {
     return gradnorm_launch(g, n, max_norm, state, nullptr, (hipStream_t)stream);
@@ -494,7 +494,8 @@ int aclgan_modeseek(const float* a, const float* b, int B, int64_t n_per_image, 
 }
 int aclgan_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* opt, int step, float decay, int mode, void* stream) {
     ACL_REQUIRE(p && g && m && v && opt, "adam: null buffer");
-    return adam_flat_ema(p, g, m, v, ema, n, opt, step, decay, mode, (hipStream_t)stream);
+    ACL_REQUIRE(ema, "adam (EMA): the average's buffer is null");
+    return adam_update({p, g, m, v, n, opt, step, ema, decay, mode}, (hipStream_t)stream);
 }
 int aclgan_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, void* stream) {
     ACL_REQUIRE(src && dst, "layout: null buffer");

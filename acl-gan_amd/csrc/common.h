@@ -253,9 +253,18 @@ struct DisView {
 };
 const int DIS_VIEW_MAX = 64;
 int dis_view(const aclgan_ctx* ctx, int net, DisView* v);
-int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, hipStream_t st);
-// the same launch with the exponential moving average of p as one more stream (mode: ACLGAN_EMA_COPY / ACLGAN_EMA_BLEND); p, m, v as adam_flat
-int adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode, hipStream_t st);
+// One Adam update of a flat buffer (optimizer.hip).  ema, state and clip may each be null: without the average (mode: ACLGAN_EMA_COPY /
+// ACLGAN_EMA_BLEND), without fp16 dynamic loss scaling (state: the bound loss-scale state; overflow scan, update with g / S or skip, scale
+// update -- all on the device), without a clip state (gradnorm_launch below, then the clipped update).  A skipped update leaves ema
+// untouched together with p, m and v.  group: whose skip counter of the loss-scale state applies.
+struct AdamUpdate {
+    float* p; const float* g; float* m; float* v; int64_t n;
+    const aclgan_adam* opt; int step;
+    float* ema = nullptr; float decay = 0.f; int mode = ACLGAN_EMA_COPY;
+    float* state = nullptr; int group = 0;
+    float* clip = nullptr; float max_norm = 0.f;
+};
+int adam_update(const AdamUpdate& u, hipStream_t st);
 int nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, hipStream_t st);
 int nhwc_to_nchw(const float* src, float* dst, int B, int C, int H, int W, hipStream_t st);
 int fill_zero(float* p, int64_t n, hipStream_t st);
@@ -264,7 +273,7 @@ int zero_async(void* p, size_t bytes, hipStream_t st);
 
 // small dense layers (MLP, style head): y[b][o] = act(sum_i x[b][i] W[o][i] + bias[o])
 int linear_fwd(int B, int I, int O, const float* x, const float* w, const float* bias, int act, float* y, hipStream_t st);
-// the generator's three-layer MLP forward in one launch (misc.hip: bit-identical to three linear_fwd calls); EUNSUPPORTED outside S <= 64, M in {64, 128, 192, 256}
+// the generator's three-layer MLP forward in one launch (dense.hip: bit-identical to three linear_fwd calls); EUNSUPPORTED outside S <= 64, M in {64, 128, 192, 256}
 bool mlp3_fwd_ok(int S, int M);
 int mlp3_fwd(int B, int S, int M, int O, const float* s, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
              const float* b2, float* m0, float* m1, float* ap, hipStream_t st);
@@ -337,11 +346,6 @@ int focus_loss_finish(const float* dec4, int64_t npix, const float* part, float 
                       const float* totals = nullptr, int64_t npix_total = 0);
 // totals[2*i], totals[2*i+1] = ordered sums of mask i's partials (mask i's partials start at part + i*2*focus_sums_blocks(npix))
 int focus_totals(const float* part, int64_t npix, int nmask, float* totals, hipStream_t st);
-// Adam under fp16 dynamic loss scaling: overflow scan, update with g/S (or skip), scale update -- all on the device
-int adam_flat_scaled(float* p, const float* g, float* m, float* v, int64_t n, const aclgan_adam* o, int step, float* state, int group, hipStream_t st);
-// ... with the average: a skipped update (overflow) leaves ema untouched together with p, m and v
-int adam_flat_scaled_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
-                         float* state, int group, hipStream_t st);
 // gradient norm and clip coefficient of a flat buffer into a clip state (gradnorm.hip; layout: include/aclgan_hip.h, aclgan_bind_grad_clip):
 // two launches.  lscale (optional): the bound loss-scale state -- the norm is taken of g / S and the pass raises lscale[3] for a non-finite g_i
 size_t grad_clip_state_floats();
@@ -354,9 +358,6 @@ size_t modeseek_scratch_floats(int B, int64_t n);
 int modeseek_part(const void* a, const void* b, int st, int B, int64_t n, float* part, hipStream_t s);
 int modeseek_grad(const void* a, const void* b, int st, int B, int64_t n, const float* part, const float* u, const float* u2, int sd, float u_scale,
                   float weight, const float* lscale, float* out4, float* da, float* db, int accumulate, hipStream_t s);
-// Adam of a buffer with a clip state: gradnorm_launch, the clipped update (ema / state optional), the scale update under a loss scale
-int adam_flat_clipped(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const aclgan_adam* o, int step, float decay, int mode,
-                      float* state, int group, float max_norm, float* clip, hipStream_t st);
 
 // spectral normalisation (spectral.hip): one power iteration + normalised weight for up to SN_MAX_LAYERS Co x K matrices in four launches;
 // u (Co) is read and overwritten, v (K) overwritten; uf / vf (optional) receive copies of the new u / v, G (optional, Co x K) is zeroed;

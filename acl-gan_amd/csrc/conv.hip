@@ -21,6 +21,7 @@
 //   * workgroup -> tile mapping is XCD-aware: the 8 XCDs each get a contiguous range of
 //     M-tiles (all N-tiles of an M-tile land on one XCD and share its L2 copy of the A rows).
 #include "common.h"
+#include "device_util.h"
 #include <cstdlib>
 
 namespace aclgan {
@@ -30,13 +31,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ int reflect_idx(int v, int n) {
     v = v < 0 ? -v : v;
     return v >= n ? 2 * (n - 1) - v : v;
-}
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == ACLGAN_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACLGAN_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
-    if (act == ACLGAN_ACT_TANH) return tanhf(v);
-    return v;
 }
 
 // block id -> logical tile id such that each XCD (block b runs on XCD b % 8) owns a contiguous
@@ -220,7 +214,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_fwd_kernel(FwdP p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m < p.M) p.y[(size_t)m * p.Co + n] = apply_act(acc[i][j][r] + bv, p.act);
+                if (m < p.M) p.y[(size_t)m * p.Co + n] = act_fwd(acc[i][j][r] + bv, p.act);
             }
         }
     }
@@ -283,7 +277,7 @@ __global__ void conv_fwd_naive_kernel(FwdP p) {
             const float* wp = p.w + (size_t)n * p.K + (ky * p.k + kx) * p.Ci;
             for (int c = 0; c < p.Ci; ++c) acc = fmaf(xp[c], wp[c], acc);
         }
-    p.y[idx] = apply_act(acc, p.act);
+    p.y[idx] = act_fwd(acc, p.act);
 }
 
 int conv_fwd_naive(const ConvGeom& g, const float* x, const float* w, const float* bias, float* y, hipStream_t st) {

@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(WM * WN * 64, OCC) conv_fwd_fast_kernel(FwdFP 
                 if (o >= 0) {
                     if (split && p.part) p.part[((size_t)blockIdx.z * p.rows + m0 + rl) * p.Co + n] = acc[i][j][r];
                     else if (split) atomicAdd(p.y + (size_t)o * p.Co + n, acc[i][j][r] + ((p.ring > 0 && blockIdx.z == 0) ? bv : 0.f));   // partial sums (ring launches: slice 0 carries the bias, act is none)
-                    else p.y[(size_t)o * p.Co + n] = act_apply(acc[i][j][r] + bv, p.act);
+                    else p.y[(size_t)o * p.Co + n] = act_fwd(acc[i][j][r] + bv, p.act);
                 }
             }
         }

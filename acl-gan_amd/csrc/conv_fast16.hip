@@ -216,7 +216,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_fwd16_kernel(FwdFP p) {
                 const int o = ro[rl];
                 if (o >= 0) {
                     if (split) p.part[((size_t)blockIdx.z * p.rows + m0 + rl) * p.Co + n] = acc[i][j][r];   // ordered partials (always)
-                    else st_st1(p.y, (int64_t)o * p.Co + n, act_apply(acc[i][j][r] + bv, p.act), p.yst);
+                    else st_st1(p.y, (int64_t)o * p.Co + n, act_fwd(acc[i][j][r] + bv, p.act), p.yst);
                 }
             }
         }
@@ -236,7 +236,7 @@ __global__ void fwd_split_finish_st_kernel(FwdFP p, int splits) {
         if (p.bias) s += *reinterpret_cast<const f32x4*>(p.bias + c4 * 4);
         st_f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = act_apply(s[e], p.act);
+        for (int e = 0; e < 4; ++e) o[e] = act_fwd(s[e], p.act);
         st_st4(p.y, ((int64_t)(b * p.Ho + oy) * p.Wo + ox) * C4 + c4, o, p.yst);
     }
 }

@@ -3,6 +3,7 @@
 // anonymous namespace: each translation unit gets its own copy (no cross-TU device symbols, no -fgpu-rdc).
 #pragma once
 #include "common.h"
+#include "device_util.h"
 #include <cstdlib>
 #include <algorithm>
 
@@ -17,12 +18,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int refl(int v, int n) {
     v = v < 0 ? -v : v;
     return v >= n ? 2 * (n - 1) - v : v;
-}
-__device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == ACLGAN_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACLGAN_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
-    if (act == ACLGAN_ACT_TANH) return tanhf(v);
-    return v;
 }
 __device__ __forceinline__ int xcd_map(int bid, int nwg) {
     const int q = nwg >> 3, r = nwg & 7;
@@ -93,7 +88,7 @@ __global__ void fwd_split_finish_kernel(FwdFP p, int splits) {
             float s = p.part[(size_t)m * p.Co + c];
             for (int z = 1; z < splits; ++z) s += p.part[((size_t)z * p.rows + m) * p.Co + c];
             if (p.bias) s += p.bias[c];
-            p.y[((size_t)(b * p.Ho + oy) * p.Wo + ox) * p.Co + c] = act_apply(s, p.act);
+            p.y[((size_t)(b * p.Ho + oy) * p.Wo + ox) * p.Co + c] = act_fwd(s, p.act);
         }
         return;
     }
@@ -108,7 +103,7 @@ __global__ void fwd_split_finish_kernel(FwdFP p, int splits) {
         if (p.bias) s += *reinterpret_cast<const f32x4*>(p.bias + c4 * 4);
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = act_apply(s[e], p.act);
+        for (int e = 0; e < 4; ++e) o[e] = act_fwd(s[e], p.act);
         *reinterpret_cast<f32x4*>(p.y + ((size_t)(b * p.Ho + oy) * p.Wo + ox) * p.Co + c4 * 4) = o;
     }
 }
@@ -151,7 +146,7 @@ __global__ void ring_zero_kernel(FwdFP p, int rows) {
 
 __global__ void bias_act_kernel(float* __restrict__ y, const float* __restrict__ bias, int Co, int act, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        y[i] = act_apply(y[i] + (bias ? bias[i % Co] : 0.f), act);
+        y[i] = act_fwd(y[i] + (bias ? bias[i % Co] : 0.f), act);
 }
 
 struct DgFP {

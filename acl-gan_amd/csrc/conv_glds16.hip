@@ -284,7 +284,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv_fwd16s_kernel(FwdSP p) {
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    float v = act_apply(acc[i][j][r] + bv, act);
+                    float v = act_fwd(acc[i][j][r] + bv, act);
                     if (p.yst != ST_F32) v = st_unpack2(st_pack2(v, 0.f, p.yst), p.yst)[0];     // the value as it will be stored
                     acc[i][j][r] = v;
                     sum += v;
@@ -319,7 +319,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv_fwd16s_kernel(FwdSP p) {
         store_acc<TM, TN>(acc, ro, wm * 64, n0 + wn * TN * 32, p.Co, p.Co, p.y, p.yst, lane, [](float v, int) { return v; });
     } else {
         store_acc<TM, TN>(acc, ro, wm * 64, n0 + wn * TN * 32, p.Co, p.Co, p.y, p.yst, lane,
-                          [&](float v, int n) { return act_apply(v + (bias ? bias[n] : 0.f), act); });
+                          [&](float v, int n) { return act_fwd(v + (bias ? bias[n] : 0.f), act); });
     }
 #endif
 }
@@ -559,7 +559,7 @@ __global__ void __launch_bounds__(512, 1) conv_fwd16p_kernel(FwdSP p) {
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    float v = act_apply(acc[i][j][r] + bv, act);
+                    float v = act_fwd(acc[i][j][r] + bv, act);
                     if (p.yst != ST_F32) v = st_unpack2(st_pack2(v, 0.f, p.yst), p.yst)[0];     // the value as it will be stored
                     acc[i][j][r] = v;
                     sum += v;
@@ -595,7 +595,7 @@ __global__ void __launch_bounds__(512, 1) conv_fwd16p_kernel(FwdSP p) {
     } else {
         __syncthreads();                           // (ro was written before the main loop's first barrier; keep the waves together for the stores)
         store_acc<TM, TN>(acc, ro, wm * 64, n0 + wn * TN * 32, p.Co, p.Co, p.y, p.yst, lane,
-                          [&](float v, int n) { return act_apply(v + (bias ? bias[n] : 0.f), act); });
+                          [&](float v, int n) { return act_fwd(v + (bias ? bias[n] : 0.f), act); });
     }
 #endif
 }

@@ -10,6 +10,7 @@
 //   wgrad   : lane = input channel, one workgroup slab = (filter row ky, a band of padded rows);
 //             every loaded activation feeds 7 taps x 4 couts = 28 FMAs with dy as scalars.
 #include "common.h"
+#include "device_util.h"
 #include <cstdlib>
 
 namespace aclgan {
@@ -21,12 +22,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ int refl(int v, int n) {
     v = v < 0 ? -v : v;
     return v >= n ? 2 * (n - 1) - v : v;
-}
-__device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == ACLGAN_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACLGAN_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
-    if (act == ACLGAN_ACT_TANH) return tanhf(v);
-    return v;
 }
 
 // ---------------- forward: Cout == 4, stride 1, no upsample, Cin % 16 == 0 ----------------
@@ -80,10 +75,10 @@ __global__ void __launch_bounds__(256) conv_fwd_co4_kernel(const float* __restri
     }
     if (oy < H && ox < W) {
         f32x4 o;
-        o[0] = act_apply(acc0 + (bias ? bias[0] : 0.f), act);
-        o[1] = act_apply(acc1 + (bias ? bias[1] : 0.f), act);
-        o[2] = act_apply(acc2 + (bias ? bias[2] : 0.f), act);
-        o[3] = act_apply(acc3 + (bias ? bias[3] : 0.f), act);
+        o[0] = act_fwd(acc0 + (bias ? bias[0] : 0.f), act);
+        o[1] = act_fwd(acc1 + (bias ? bias[1] : 0.f), act);
+        o[2] = act_fwd(acc2 + (bias ? bias[2] : 0.f), act);
+        o[3] = act_fwd(acc3 + (bias ? bias[3] : 0.f), act);
         *reinterpret_cast<f32x4*>(y + ((size_t)(b * H + oy) * W + ox) * 4) = o;
     }
 }
@@ -254,7 +249,7 @@ __global__ void __launch_bounds__(256) conv_thin_out_kernel(const float* __restr
         for (int v = 0; v < 4; ++v) {
             const int pl = 4 * (lane >> 2) + v;                 // the lane whose pixel this register belongs to
             const int oy = ty0 + 2 * wave + (pl >> 5), ox = tx0 + (pl & 31);
-            if (oy < Ho && ox < Wo) out[((size_t)(b * Ho + oy) * Wo + ox) * CN + co] = act_apply(r[v] + bv, act);
+            if (oy < Ho && ox < Wo) out[((size_t)(b * Ho + oy) * Wo + ox) * CN + co] = act_fwd(r[v] + bv, act);
         }
     }
 }
@@ -602,8 +597,8 @@ __global__ void __launch_bounds__(256, 2) conv_thin_in2_kernel(const float* __re
             for (int r = 0; r < 16; ++r) {
                 const int oxl = (r & 3) + 8 * (r >> 2);
                 if (oxl < wlim) {
-                    orow[oxl * 64] = act_apply(acc[i][0][r] + bv0, act);
-                    orow[oxl * 64 + 32] = act_apply(acc[i][1][r] + bv1, act);
+                    orow[oxl * 64] = act_fwd(acc[i][0][r] + bv0, act);
+                    orow[oxl * 64 + 32] = act_fwd(acc[i][1][r] + bv1, act);
                 }
             }
         }

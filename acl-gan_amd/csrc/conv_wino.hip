@@ -17,6 +17,7 @@
 // pipeline on dy with ZERO padding and the flipped / transposed filter for the interior of dx (the halo ring of the padded grid
 // keeps its small direct launch, conv_fast.hip mode 2).  The weight gradient stays on the direct kernel.
 #include "common.h"
+#include "device_util.h"
 #include "st16.h"
 #include <atomic>
 #include <cstdlib>
@@ -59,12 +60,6 @@ __device__ __forceinline__ int reflw(int v, int n) {
     v = v < 0 ? -v : v;
     return v >= n ? 2 * (n - 1) - v : v;
 }
-__device__ __forceinline__ float actw(float v, int act) {
-    if (act == ACLGAN_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACLGAN_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
-    if (act == ACLGAN_ACT_TANH) return tanhf(v);
-    return v;
-}
 
 // the transform kernels move NV channels per thread (NHWC: NV consecutive floats = one 4 / 8 / 16-byte access)
 template <int NV> struct VecOf { typedef float T __attribute__((ext_vector_type(NV))); };
@@ -72,10 +67,10 @@ template <> struct VecOf<1> { typedef float T; };
 template <int NV> __device__ __forceinline__ typename VecOf<NV>::T actv(typename VecOf<NV>::T v, int act) {
     if (act == ACLGAN_ACT_NONE) return v;
 #pragma unroll
-    for (int e = 0; e < NV; ++e) v[e] = actw(v[e], act);
+    for (int e = 0; e < NV; ++e) v[e] = act_fwd(v[e], act);
     return v;
 }
-template <> __device__ __forceinline__ float actv<1>(float v, int act) { return actw(v, act); }
+template <> __device__ __forceinline__ float actv<1>(float v, int act) { return act_fwd(v, act); }
 
 // B^T d (input transform along one axis), G g (filter), A^T m (output)
 template <typename F>

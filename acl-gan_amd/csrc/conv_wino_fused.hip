@@ -24,6 +24,7 @@
 // LDS patch layout: units of 8 bytes (one channel pair), unit(q, r, c) = (q * 18 + r) * 42 + (c & 3) * 9 + (c >> 2): the 32 lanes of
 // a ds_read_b64 group (8 tile columns x 4 tile rows) read units const + 168 * ty + tx = const + 8 ty + tx (mod 32): conflict-free.
 #include "common.h"
+#include "device_util.h"
 #include <cstdlib>
 #include <algorithm>
 #include <cmath>
@@ -66,12 +67,6 @@ struct WfP {
 __device__ __forceinline__ int reflf(int v, int n) {
     v = v < 0 ? -v : v;
     return v >= n ? 2 * (n - 1) - v : v;
-}
-__device__ __forceinline__ float actf(float v, int act) {
-    if (act == ACLGAN_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACLGAN_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
-    if (act == ACLGAN_ACT_TANH) return tanhf(v);
-    return v;
 }
 
 __device__ __forceinline__ void at4f(const float (&m)[6], float (&y)[4]) {

@@ -1,50 +1,17 @@
-// elementwise.hip -- the HBM-bound kernels of the ACL-GAN step (gfx950): normalisation layers
-// (+activation, +residual) forward/backward, pooling, focus blend, losses, Adam, small dense
-// layers, layout conversion.  Activations NHWC ([B][HW][C]), stored fp32 or -- wide layers of the 16-bit compute dtypes -- bf16 / fp16
-// (st16.h: storage code per tensor, statistics / coefficients / arithmetic always fp32).
+// elementwise.hip -- the normalisation layers of the ACL-GAN step (gfx950), HBM-bound: instance norm, AdaIN and layer norm
+// (+activation, +residual) forward and backward.  Activations NHWC ([B][HW][C]), stored fp32 or -- wide layers of the 16-bit compute
+// dtypes -- bf16 / fp16 (st16.h: storage code per tensor, statistics / coefficients / arithmetic always fp32).
 //
 // Reference semantics restated here (file:line into the reference tree):
 //   InstanceNorm2d(affine=False)          networks.py:333   biased var, 1/sqrt(var+1e-5)
 //   AdaptiveInstanceNorm2d                networks.py:491-503 (F.batch_norm on a (1,B*C,H,W) view)
 //   custom LayerNorm                      networks.py:520-536 unbiased std, 1/(std+1e-5), gamma/beta per channel
 //   ResBlock  out += residual             networks.py:309
-//   AvgPool2d(3,2,1,count_include_pad=F)  networks.py:33
-//   focus_translation / focus losses      trainer.py:85-88, 146-161
-//   LSGAN losses / L1                     networks.py:67,83,98 / trainer.py:61-62
-//   Adam (L2 weight decay)                trainer.py:39-42
 #include "common.h"
+#include "device_util.h"
 #include "st16.h"
 
 namespace aclgan {
-
-__device__ __forceinline__ float act_fwd(float v, int act) {
-    if (act == ACLGAN_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACLGAN_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
-    if (act == ACLGAN_ACT_TANH) return tanhf(v);
-    return v;
-}
-// derivative of the activation expressed through its OUTPUT y
-__device__ __forceinline__ float act_grad(float y, int act) {
-    if (act == ACLGAN_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (act == ACLGAN_ACT_LRELU) return y > 0.f ? 1.f : 0.2f;
-    if (act == ACLGAN_ACT_TANH) return 1.f - y * y;
-    return 1.f;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// block-wide sum for 256-thread blocks; result valid in every thread
-__device__ __forceinline__ float block_sum256(float v, float* red /*[4]*/) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // Chan et al. pairwise combination of (count, mean, M2)
 __device__ __forceinline__ void chan_combine(float& n, float& mean, float& m2, float nb, float meanb, float m2b) {

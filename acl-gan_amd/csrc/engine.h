@@ -215,7 +215,7 @@ struct aclgan_ctx {
     int aug_policy = 0;
     const float* aug_params = nullptr;
     int aug_rows = 0;
-    // ---- LeCam regularisation of the discriminators (aclgan_ctx_set_lecam; misc.hip: lsgan_lecam_batch / lecam_fold).
+    // ---- LeCam regularisation of the discriminators (aclgan_ctx_set_lecam; losses.hip: lsgan_lecam_batch / lecam_fold).
     // lecam_state null: off -- dis_lsgan builds exactly the launches it built before the feature existed.  Otherwise the train passes that
     // dis_update_impl builds (in_dis_update: set for the body of that function, real or dry, and nowhere else -- the fold that consumes the
     // statistics follows only there) run the term kernel with the anchors of their discriminator, and the update ends with the fold.

@@ -733,16 +733,20 @@ int aclgan_zero_grad(aclgan_ctx* ctx, int group, void* stream) {
     ACL_REQUIRE(g.grad, "gradient buffer not bound");
     return fill_zero(g.grad, g.numel, (hipStream_t)stream);
 }
-int aclgan_adam_step(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int step, void* stream) {
-    ACL_REQUIRE(ctx && opt && group >= 0 && group <= 1, "bad ctx/group/opt");
+// the update of a bound group with whatever the context has bound for it: loss-scale state, clip state
+static int group_adam_update(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int step, float* ema, float decay, int mode, void* stream) {
     Group& g = ctx->groups[group];
     ACL_REQUIRE(g.param && g.grad && g.m && g.v, "param/grad/exp_avg/exp_avg_sq must all be bound");
     if (group == ACLGAN_GROUP_GEN) ctx->carry_drop();      // (the generators move: kept encodings are stale)
-    if (ctx->clip[group])
-        return adam_flat_clipped(g.param, g.grad, g.m, g.v, nullptr, g.numel, opt, step, 0.f, ACLGAN_EMA_COPY, ctx->lscale, group, ctx->clip_max[group],
-                                 ctx->clip[group], (hipStream_t)stream);
-    if (ctx->lscale) return adam_flat_scaled(g.param, g.grad, g.m, g.v, g.numel, opt, step, ctx->lscale, group, (hipStream_t)stream);
-    return adam_flat(g.param, g.grad, g.m, g.v, g.numel, opt, step, (hipStream_t)stream);
+    AdamUpdate u = {g.param, g.grad, g.m, g.v, g.numel, opt, step};
+    u.ema = ema; u.decay = decay; u.mode = mode;
+    u.state = ctx->lscale; u.group = group;
+    u.clip = ctx->clip[group]; u.max_norm = ctx->clip_max[group];
+    return adam_update(u, (hipStream_t)stream);
+}
+int aclgan_adam_step(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int step, void* stream) {
+    ACL_REQUIRE(ctx && opt && group >= 0 && group <= 1, "bad ctx/group/opt");
+    return group_adam_update(ctx, group, opt, step, nullptr, 0.f, ACLGAN_EMA_COPY, stream);
 }
 
 int aclgan_bind_ema(aclgan_ctx* ctx, int group, float* ema) {
@@ -756,14 +760,7 @@ int aclgan_bind_ema(aclgan_ctx* ctx, int group, float* ema) {
 int aclgan_adam_step_ema(aclgan_ctx* ctx, int group, const aclgan_adam* opt, int step, float decay, int mode, void* stream) {
     ACL_REQUIRE(ctx && opt, "bad ctx/opt");
     ACL_REQUIRE(group == ACLGAN_GROUP_GEN && ctx->ema, "adam_step_ema: no averaged copy is bound for group %d (aclgan_bind_ema)", group);
-    Group& g = ctx->groups[group];
-    ACL_REQUIRE(g.param && g.grad && g.m && g.v, "param/grad/exp_avg/exp_avg_sq must all be bound");
-    ctx->carry_drop();
-    if (ctx->clip[group])
-        return adam_flat_clipped(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, ctx->lscale, group, ctx->clip_max[group],
-                                 ctx->clip[group], (hipStream_t)stream);
-    if (ctx->lscale) return adam_flat_scaled_ema(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, ctx->lscale, group, (hipStream_t)stream);
-    return adam_flat_ema(g.param, g.grad, g.m, g.v, ctx->ema, g.numel, opt, step, decay, mode, (hipStream_t)stream);
+    return group_adam_update(ctx, group, opt, step, ctx->ema, decay, mode, stream);
 }
 size_t aclgan_grad_clip_state_floats(void) { return grad_clip_state_floats(); }
 int aclgan_bind_grad_clip(aclgan_ctx* ctx, int group, float max_norm, float* state) {

@@ -436,7 +436,7 @@ int decode(aclgan_ctx& c, int net, bool train, Act* content, Act* style, Act** o
     const int C = content->C, nr = a.gen_n_res, nad = 2 * C * 2 * nr;
     // MLP (networks.py:280-292)
     Act *m0 = nullptr, *m1 = nullptr, *ap = nullptr;
-    // (round 6) one launch for the three layers where the widths allow (misc.hip: mlp3_fwd -- the same bits as three linear_fwd launches);
+    // (round 6) one launch for the three layers where the widths allow (dense.hip: mlp3_fwd -- the same bits as three linear_fwd launches);
     // activations, accounting and the three backward closures are those of dense()
     const int sdim = style->H * style->W * style->C;
     const bool fused = sw(SW_MLP_FUSED) && mlp3_fwd_ok(sdim, a.gen_mlp_dim);

@@ -2,9 +2,9 @@
 Per group, over the same flat buffers, each figure the time of one call from stream events around `--reps` back-to-back calls:
     copy             a device-to-device copy of the gradient buffer (4 B read + 4 B written per parameter): the rate the bytes are held against
     norm             aclgan_grad_clip_flat: gradnorm_part_kernel + gradnorm_finish_kernel (4 B / parameter read)
-    adam_fp32        aclgan_adam_step without a state (adam_kernel)                 adam_fp32_clip   with one: part, finish, adam_clip_kernel
-    adam_fp16        aclgan_adam_step under a loss scale: grad_check_kernel, adam_scaled_kernel, scale_update_kernel
-    adam_fp16_clip   the same with a state: part, finish, adam_scaled_clip_kernel, scale_update_kernel
+    adam_fp32        aclgan_adam_step without a state (adam_kernel)                 adam_fp32_clip   with one: part, finish, adam_kernel<CLIP>
+    adam_fp16        aclgan_adam_step under a loss scale: grad_check_kernel, adam_kernel<SCALED>, scale_update_kernel
+    adam_fp16_clip   the same with a state: part, finish, adam_kernel<SCALED, CLIP>, scale_update_kernel
 adam_fp16_clip - adam_fp16 is the norm stage against the scan it replaces (part + finish - grad_check_kernel): the other two launches are
 the same work.  The variants are measured in turn, `--rounds` times; reported: median and range over the rounds.
 --step: one dis + gen step of the trainer at 256x256, B = 8, fp32 and bf16, grad_clip off against grad_clip: .inf.

@@ -1,6 +1,6 @@
 """The averaged generator on the GPU.
 
-Operator level (adam_ema_kernel / adam_scaled_ema_kernel of csrc/misc.hip through aclgan_adam_flat_ema and, for the loss-scaled path,
+Operator level (the EMA instantiations of adam_kernel, csrc/optimizer.hip, through aclgan_adam_flat_ema and, for the loss-scaled path,
 a context with aclgan_bind_loss_scale + aclgan_bind_ema + aclgan_adam_step_ema):
   p, m, v bit-identical to the launch without the average; the average against its formula in fp64 from the same fp32 inputs; copy mode
   (also over a non-finite old average); a skipped fp16 update leaves everything untouched.

@@ -1,5 +1,5 @@
 """Gradient norm per group: readout, clipping and the non-finite guard on the GPU -- gradnorm_part_kernel / gradnorm_finish_kernel of
-csrc/gradnorm.hip and the clipped Adam kernels of csrc/misc.hip against the fp64 model of tests/gradclip_ref.py.
+csrc/gradnorm.hip and the clipped Adam kernels of csrc/optimizer.hip against the fp64 model of tests/gradclip_ref.py.
 
   (1) the norm stage alone (aclgan_grad_clip_flat) at the edges of its decomposition, aligned and from a pointer offset by one float:
       relative error against the fp64 norm of the same fp32 buffer <= 1e-5 (the bound of this project's other fixed-order sums), the

@@ -770,7 +770,7 @@ def _rel64(a, b):
 @pytest.mark.parametrize("B,mode", _modes([3, 4, 8, 32]), indirect=["mode"])
 def test_dense_layers_at_step_batches(L, B, mode):
     """the style MLP (8 -> 256 -> 256 -> 4096, one fused launch), its linear layers forward / backward, the style head (256 -> 8).  The input
-    gradient of the 256 -> 4096 layer combines O-slices with fp32 atomics in the default plan (misc.hip linear_dx, O >= 512), one slice in
+    gradient of the 256 -> 4096 layer combines O-slices with fp32 atomics in the default plan (dense.hip linear_dx, O >= 512), one slice in
     the deterministic plan"""
     chk = Check("B=%d" % B, mode)
     gen = torch.Generator(device="cuda").manual_seed(B)

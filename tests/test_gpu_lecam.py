@@ -1,4 +1,4 @@
-"""LeCam regularisation of the discriminators on the GPU (csrc/misc.hip: lsgan_lecam_batch_kernel / lecam_fold_kernel; aclgan_ctx_set_lecam;
+"""LeCam regularisation of the discriminators on the GPU (csrc/losses.hip: lsgan_lecam_batch_kernel / lecam_fold_kernel; aclgan_ctx_set_lecam;
 config keys lecam_lambda / lecam_decay / lecam_start): the operator against fp64 numpy, dis_update against the fp32 oracle with its lsgan
 wrapped (tests/lecam_ref.py), the anchor recurrence, the bits before the start, launch counts, lanes and graph replay, fp16, checkpoints
 and the error paths.  Run on the GPU box: pytest -m gpu"""

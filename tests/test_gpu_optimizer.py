@@ -1,4 +1,4 @@
-"""aclgan_adam_step -- adam_kernel, grad_check_kernel, adam_scaled_kernel and scale_update_kernel of csrc/misc.hip -- against the fp64
+"""aclgan_adam_step -- adam_kernel (plain and SCALED), grad_check_kernel and scale_update_kernel of csrc/optimizer.hip -- against the fp64
 optimizer model of oracle/optimizer_oracle.py (itself checked on the CPU by tests/test_optimizer_oracle_cpu.py).
 
 Everything goes through the C ABI with a real context: aclgan_ctx_create, aclgan_bind_params for both groups and, for the fp16 path,

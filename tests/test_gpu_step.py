@@ -151,7 +151,7 @@ def test_update_steps_match_reference(T, fix, ltol, gtol):
 
     for n, v in meta["losses"].items():
         got = float(getattr(trd if n.startswith("loss_dis") else trg, n))
-        tol = 5e-3 if n.endswith("_size") else ltol    # centred, ordered summation (misc.hip: focus_sums_kernel)
+        tol = 5e-3 if n.endswith("_size") else ltol    # centred, ordered summation (losses.hip: focus_sums_kernel)
         assert abs(got - v) <= tol * max(1e-3, abs(v)), (n, got, v)
 
     gmax = max(v[1] for v in meta["grad_stats"].values())
